@@ -17,6 +17,12 @@ DNJ (ccg_tree_shard_dev, exact) consumes them over RCCL -- strong scaling of
 one pipeline, `scaling: "strong"`.  `joins_sha256` is the hash of the join
 list, identical for every N when the sharded tree equals the single-GPU one.
 
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K
+steps and prints the line; `--dump-outputs DIR` also writes what the last
+timed step returned (dump_outputs).  Everything below -- the profiled step
+behind the tree kernels' rooflines and the reference-rule cells, the CPU
+baselines, the extras -- runs only with `--full`.
+
 Roofline: the dominant kernel by device time of the step (the MFMA dist
 kernel at N = 1; its duration from HIP events on the engine stream,
 ccg_last_dist_ms), with every tree kernel class beside it (HIP events of a
@@ -92,6 +98,7 @@ def _latest(*names):
 
 PMC_SUMMARY = _latest("r06_pmc.json", "r05_pmc.json", "r04_pmc.json", "r03_pmc.json", "r02_pmc.json")
 PMC_HEADLINE = _latest("r06_pmc_headline.json", "r05_pmc_headline.json", "r04_pmc_headline.json", "r03_pmc_headline.json")
+LT_SAMPLE_CELLS = 1 << 20      # --dump-outputs: cells of the last step's LT (8 MB as f64)
 SHARD_LEG_TIMEOUT_S = 600
 HEADLINE_TIMEOUT_S = 1200
 
@@ -533,7 +540,7 @@ def make_headline_alignment(torch, n, L, seed=3):
 
 
 def pipeline_leg(dev, torch, rank, world, dist, coll, n, L, steps, warmup, barrier, profile_tree=True, capture_k=0,
-                 tree_mode="shard", pg=None, tree_cus=0, tree_layout="low", seed=3):
+                 tree_mode="shard", pg=None, tree_cus=0, tree_layout="low", seed=3, sample_lt=0):
     """The headline: dist + exact DNJ of one n x L alignment per step.
     world 1: ccg_snp_ltd_dev into the full double LT, ccg_tree_dev in place;
     world > 1, tree_mode "shard": ccg_snp_ltd_shard_dev into this rank's band
@@ -547,9 +554,11 @@ def pipeline_leg(dev, torch, rank, world, dist, coll, n, L, steps, warmup, barri
     Returns (timed result, the last step's joins, profiled-step stats or None,
     alignment, the first capture_k LT cells of the first step (world 1)).
     world 1 with tree_cus > 0: the pipelined form (pipelined_leg, alignments
-    of seeds 3 and 4 in turn); otherwise the alignment of `seed`."""
+    of seeds 3 and 4 in turn); otherwise the alignment of `seed`.
+    sample_lt (pipelined form only): res["lt_sample"], see pipelined_leg."""
     if world == 1 and tree_cus > 0:
-        return pipelined_leg(dev, torch, n, L, steps, warmup, barrier, tree_cus, profile_tree, capture_k, tree_layout)
+        return pipelined_leg(dev, torch, n, L, steps, warmup, barrier, tree_cus, profile_tree, capture_k, tree_layout,
+                             sample_lt)
     if world > 1 and tree_mode == "gather-pipelined":
         return gather_pipelined_leg(dev, torch, rank, world, dist, n, L, steps, warmup, barrier, pg, profile_tree)
     import hashlib
@@ -649,6 +658,31 @@ def pipeline_leg(dev, torch, rank, world, dist, coll, n, L, steps, warmup, barri
     return res, joins, pst, (seqs, incs, W), (cap[0] if cap else None)
 
 
+def lt_sample_index(m, count, seed=17):
+    """A fixed, sorted sample of `count` of the m LT cells (all of them when
+    m <= count): the same cells for every build and run."""
+    if m <= count:
+        return np.arange(m, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).integers(0, m, size=count, dtype=np.int64))
+
+
+def dump_outputs(path, joins, included_positions, lt_sample=None):
+    """--dump-outputs: what the last timed step returned, one float64 .npy per
+    array: the join list by column (joins_i, joins_j, joins_Li, joins_Lj), the
+    final pair (final_pair: node, distance), the dist's included positions,
+    and (pipelined form) a fixed sample of the LT cells that step's dist wrote
+    (lt_sample, lt_sample_index's cells)."""
+    jj, fn, fd = joins
+    os.makedirs(path, exist_ok=True)
+    out = {"joins_" + f: np.ascontiguousarray(jj[f], dtype=np.float64) for f in ("i", "j", "Li", "Lj")}
+    out["final_pair"] = np.array([fn, fd], dtype=np.float64)
+    out["included_positions"] = np.array([included_positions], dtype=np.float64)
+    if lt_sample is not None:
+        out["lt_sample"] = np.ascontiguousarray(lt_sample, dtype=np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def tree_cu_set(ncu, k, layout):
     """The tree context's compute units.  Mask bit c runs on XCD c % 8 (slot
     c // 8 there; tools/micro/cu_mask.hip, profiles/r06_cu_mask_map.txt), so
@@ -665,7 +699,8 @@ def tree_cu_set(ncu, k, layout):
     return list(range(k))
 
 
-def pipelined_leg(dev, torch, n, L, steps, warmup, barrier, tree_cus, profile_tree=True, capture_k=0, layout="low"):
+def pipelined_leg(dev, torch, n, L, steps, warmup, barrier, tree_cus, profile_tree=True, capture_k=0, layout="low",
+                  sample_lt=0):
     """The headline on one GPU as a pipeline over a stream of alignments: two
     engine contexts on disjoint compute units (ccg_ctx_configure: the tree's
     stream on CUs [0, tree_cus), 8 per XCD, the dist's on the rest, neither
@@ -678,7 +713,10 @@ def pipelined_leg(dev, torch, n, L, steps, warmup, barrier, tree_cus, profile_tr
     rate is matrices completed per second in steady state.  tree_s / dist_s
     are each context's device time (HIP events on its own stream); the thread
     walls are reported beside them.  Same return value as pipeline_leg, plus
-    res["alignments"] (both) and res["joins_sha256_by_alignment"]."""
+    res["alignments"] (both) and res["joins_sha256_by_alignment"]; with
+    sample_lt > 0 also res["lt_sample"], that many cells (lt_sample_index) of
+    the LT the last timed step's dist wrote (the next matrix's: the tree
+    consumes its own in place), read after the timed region."""
     import hashlib
     import threading
     import ccphylo_amd as cg
@@ -754,13 +792,18 @@ def pipelined_leg(dev, torch, n, L, steps, warmup, barrier, tree_cus, profile_tr
     joins, st, inc = parts[-1][3], parts[-1][4], parts[-1][5]
     # the line's sha: alignment 0's (the sequential form's default matrix)
     sha = sorted(shas[0])[0] if 0 in shas else sha_of(joins)
+    lt_sample = None
+    if sample_lt and steps:   # before the profiled step's tree consumes that LT
+        idx = torch.from_numpy(lt_sample_index(m, sample_lt)).to("cuda")
+        lt_sample = Ds[k % 2][idx].cpu().numpy()
+        del idx
     pst = step(k, profile=True)[4] if profile_tree else None   # an extra, untimed pipelined step
     res = {"dt": dt, "dist_s": sum(p[2] for p in parts) / steps / 1e3, "tree_s": sum(p[6] for p in parts) / steps,
            "dist_wall_s": sum(p[0] for p in parts) / steps, "tree_wall_s": sum(p[1] for p in parts) / steps,
            "dist_kernel_ms": sum(p[2] for p in parts) / steps, "joins": len(joins[0]), "joins_sha256": sha,
            "joins_sha256_by_alignment": {str(a): sorted(v) for a, v in shas.items()},
            "rows_rescanned": int(st[0]), "cells_rescanned": int(st[1]), "included_positions": inc,
-           "alignments": aligns,
+           "alignments": aligns, "lt_sample": lt_sample,
            "pipelined": {"tree_cus": tree_cus, "dist_cus": ncu - tree_cus, "layout": layout,
                          "matrix0_included_positions": inc0, "alignment_seeds": [3, 4]}}
     del Ds
@@ -1325,8 +1368,15 @@ def main():
     ap.add_argument("--n", "--taxa", dest="n", type=int, default=50_000,
                     help="headline taxa (configs[2]; --taxa under torchrun, whose own options take --n)")
     ap.add_argument("--L", type=int, default=5_000_000, help="headline alignment length (configs[2])")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: a profiled step "
+                         "(the tree kernels' rooflines, the reference-rule cells), the reference CPU baselines and "
+                         "the extras (configs[1], configs[3], dist alone, KMA, sharded NJ); without it the run sets "
+                         "up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64; dump_outputs)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: without the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: without the extras")
     ap.add_argument("--c1-n", type=int, default=10_000)
     ap.add_argument("--refrule-prefix", type=int, default=150)
     ap.add_argument("--shard-n", type=int, default=100_000)
@@ -1353,6 +1403,8 @@ def main():
     ap.add_argument("--headline-seed", type=int, default=3,
                     help="the alignment's seed in the sequential forms (the pipelined one alternates 3 and 4)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: the headline only
+        args.no_cpu = args.no_extras = True
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
     env_world = os.environ.get("WORLD_SIZE")
@@ -1428,10 +1480,13 @@ def main():
         hwd.start()
     head, joins, pst, (seqs, incs, W), cells = pipeline_leg(
         dev, torch, rank, world, dist if world > 1 else None, coll, n, L, args.steps, args.warmup, barrier,
+        profile_tree=args.full, sample_lt=LT_SAMPLE_CELLS if args.dump_outputs else 0,
         capture_k=256 * 255 // 2 if (world == 1 and not args.no_cpu) else 0, tree_mode=args.tree_mode, pg=pg,
         tree_cus=args.tree_cus if world == 1 else 0, tree_layout=args.tree_layout, seed=args.headline_seed)
     if hwd is not None:
         hwd.cancel()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, joins, head["included_positions"], head.pop("lt_sample", None))
     dt = head["dt"]
     # dist launches per call (snp_launch_mfma2: 256 x 256 tiles in batches of
     # 65536; no split-K at the headline's tile count)

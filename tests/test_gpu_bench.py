@@ -31,6 +31,43 @@ def test_bench_world_mismatch_refused():
 
 
 @pytest.mark.gpu
+def test_bench_plain_full_dump_outputs(tmp_path):
+    """A plain run times the headline only (no profiled step, CPU baseline or
+    extras; the dist kernel alone in the roofline); --full adds the profiled
+    step's tree kernels.  --dump-outputs writes the last timed step's results
+    as float64 arrays, the same from run to run (seeded inputs)."""
+    import numpy as np
+    plain = _bench(["--gpus", "1", "--n", "3000", "--L", "20000", "--steps", "2", "--warmup", "1",
+                    "--dump-outputs", str(tmp_path / "a")])
+    full = _bench(["--gpus", "1", "--full", "--dump-outputs", str(tmp_path / "b")] + SMALL +
+                  ["--steps", "2", "--warmup", "1"])
+    for p in (plain, full):
+        assert p.returncode == 0, p.stderr[-3000:]
+    lp, lf = (json.loads(p.stdout.strip().splitlines()[-1]) for p in (plain, full))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in lp and key in lf
+    assert lp["steps"] == 2 and lp["ms_per_step"] > 0
+    # value = pairs per step time; ms_per_step is rounded to 0.1 ms (off by at most 0.05), value to 0.1
+    assert abs(lp["value"] * lp["ms_per_step"] / 1e3 / (3000 * 2999 // 2) - 1) <= 0.1 / lp["ms_per_step"]
+    assert "extras" not in lp and "cpu_baseline" not in lp and set(lp["roofline"]["kernels"]) == {"dist"}
+    assert len(lf["roofline"]["kernels"]) > 1
+    assert lp["split"]["joins_sha256"] == lf["split"]["joins_sha256"]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) == [
+        "final_pair.npy", "included_positions.npy", "joins_Li.npy", "joins_Lj.npy", "joins_i.npy", "joins_j.npy",
+        "lt_sample.npy"]
+    total = 0
+    for nm in names:
+        a, b = np.load(tmp_path / "a" / nm), np.load(tmp_path / "b" / nm)
+        assert a.dtype == np.float64 and a.shape == b.shape and np.array_equal(a, b), nm
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert len(np.load(tmp_path / "a" / "joins_i.npy")) == 2998
+    lt = np.load(tmp_path / "a" / "lt_sample.npy")   # SNP counts of 20000 positions, every 10th word excluded
+    assert len(lt) == 1 << 20 and (lt == np.round(lt)).all() and lt.min() >= 0 and lt.max() <= 20000
+
+
+@pytest.mark.gpu
 def test_bench_gpus2_spawned_same_joins():
     """--gpus 1 pipelined and sequential; --gpus 2 (ranks spawned by bench.py,
     gloo rehearsal on one GPU) in every tree mode: GPU 0's tree beside the

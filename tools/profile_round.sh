@@ -11,7 +11,7 @@ R=$PWD
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-echo "== bench" && timeout -k 10 600 python3 $R/bench.py > $OUT/bench.json 2> $OUT/bench.err || exit 1
+echo "== bench" && timeout -k 10 600 python3 $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err || exit 1
 tail -c 400 $OUT/bench.json
 echo "== kernel trace" && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 $R/bench.py --steps 1 --warmup 0 --no-extras --no-cpu > $OUT/trace.log 2>&1 || exit 1
 echo "== pmc FETCH_SIZE" && timeout -k 10 420 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o run -- python3 $R/tools/perf_dnj.py 10000 dnj exact > $OUT/pmc_fetch.log 2>&1 || exit 1
