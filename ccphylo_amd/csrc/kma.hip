@@ -43,7 +43,7 @@ __device__ __forceinline__ Cnt unpack(uint4 w) {
 // ------------------------------------------------------------------ metrics
 template <int M>
 __device__ __forceinline__ double kma_metric(const Cnt &x, const Cnt &y, double s1, double s2, unsigned ln) {
-	if constexpr(M == CCG_KMA_COS) {   // matcmp.c:420; s = sqrt(sum c^2), 0 iff the sum is 0
+	if constexpr(M == CCG_KMA_COS) {   // matcmp.c:420; s: k_kma_norms (0 iff the sum is 0, NaN iff negative)
 		long long dot = 0;
 #pragma unroll
 		for(int k = 0; k < 5; ++k) dot += imul32(x.c[k], y.c[k]);
@@ -195,15 +195,21 @@ __device__ __forceinline__ double kma_metric(const Cnt &x, const Cnt &y, double 
 	}
 }
 
-// cos: sqrt of the sum of squares of components 0..4 per row (an unsigned
-// long of wrapped int products in the reference), 0 iff that sum is 0
+// cos: sqrt of the sum of squares of components 0..4 per row.  The reference
+// (matcmp.c:428-437) adds int products to an unsigned long; a count >= 46341
+// overflows the product, which C leaves undefined, so the reference BINARY is
+// the arbiter: it wraps the product to 32 bits, sign-extends it into the
+// 64-bit sum and converts that sum to double as SIGNED.  So the norm is 0 iff
+// the sum is 0 (kma_metric returns -1) and NaN iff the sum is negative: NaN
+// fails `s == 0`, makes d NaN, passes the clamp `d < 0 ? 0 : d` unchanged and
+// fails `0 <= d` in k_kma_pairs -- the position is dropped, as in the binary.
 __global__ void k_kma_norms(const uint4 *__restrict__ rec, long long rows, double *__restrict__ s) {
 	for(long long k = (long long) blockIdx.x * blockDim.x + threadIdx.x; k < rows;
 	    k += (long long) gridDim.x * blockDim.x) {
 		const Cnt x = unpack(rec[k]);
-		unsigned long long c = 0;
+		long long c = 0;
 #pragma unroll
-		for(int t = 0; t < 5; ++t) c += (unsigned long long) (long long) imul32(x.c[t], x.c[t]);
+		for(int t = 0; t < 5; ++t) c += imul32(x.c[t], x.c[t]);
 		s[k] = sqrt((double) c);
 	}
 }

@@ -131,11 +131,10 @@ static void parse_sample(Sample *s) {
 	free(p);
 }
 
-/* matcmp.c:27 stripMat on a copy of the loaded buffer: rows with ref '-' are
+/* matcmp.c:27 stripMat on the loaded buffer `out`: rows with ref '-' are
  * squeezed out with a 7-short stride (the reference's rows are 8 shorts), and
  * without any such row the length comes out one larger.  Returns the length. */
 static int strip_rows(const Sample *s, uint16_t *out) {
-	memcpy(out, s->buf, (size_t) s->rows * 16);
 	int left = s->rows + 1, len = 0;
 	const unsigned char *ref = s->refs;
 	while(left && *ref != '-') {
@@ -254,11 +253,33 @@ ccq_kma *ccq_load_kma(char **files, int nfiles, const char *tmpl, unsigned minDe
 	K->len1 = calloc((size_t) (n ? n : 1), 4);
 	K->len2 = calloc((size_t) (n ? n : 1), 4);
 	K->file_of = calloc((size_t) (n ? n : 1), 4);
-	if(!K->rec1 || !K->rec2 || !K->len1 || !K->len2 || !K->file_of) abort();
+	/* The reference loads every row sample into ONE buffer (mat1, dist.c:113)
+	 * that FileBuffLoadMat (matparse.c:213) never clears: a load overwrites
+	 * rows 0 .. rows-1, and the row behind them keeps what earlier samples
+	 * left there after their stripMat (zero if none reached it: the 16 MiB
+	 * buffer comes as fresh zero pages).  Without insertion rows stripMat
+	 * returns rows + 1, so cmpMats compares that leftover row with the last
+	 * row of a column sample of exactly rows + 1 rows.  `mat1` replays the
+	 * buffer in file order -- samples that fail the thresholds are loaded
+	 * too, but not stripped (ltdmatrixthrd.c:495-530) -- and rec1 takes each
+	 * included sample's rows 0 .. rows from it. */
+	int64_t mrows = 1;
+	for(int k = first < 0 ? nfiles : first + 1; k < nfiles; ++k) {
+		if(S[k].found && S[k].rows + 1 > mrows) mrows = S[k].rows + 1;
+	}
+	uint16_t *mat1 = calloc((size_t) mrows, 16);
+	if(!K->rec1 || !K->rec2 || !K->len1 || !K->len2 || !K->file_of || !mat1) abort();
 	for(int k = 0, r = 0; k < nfiles; ++k) {
+		if(k > first && first >= 0 && S[k].found) memcpy(mat1, S[k].buf, (size_t) S[k].rows * 16);
 		if(!K->include[k]) continue;
 		K->file_of[r] = k;
-		K->len1[r] = strip_rows(&S[k], K->rec1 + (size_t) r * st1 * 8);
+		if(k > first) {
+			K->len1[r] = strip_rows(&S[k], mat1);
+			memcpy(K->rec1 + (size_t) r * st1 * 8, mat1, (size_t) (S[k].rows + 1) * 16);
+		} else {   /* the first sample is never a row sample: its own rows, stripped */
+			memcpy(K->rec1 + (size_t) r * st1 * 8, S[k].buf, (size_t) S[k].rows * 16);
+			K->len1[r] = strip_rows(&S[k], K->rec1 + (size_t) r * st1 * 8);
+		}
 		uint16_t *o = K->rec2 + (size_t) r * st2 * 8;
 		int m = 0;
 		for(int q = 0; q < S[k].rows; ++q) {
@@ -267,6 +288,7 @@ ccq_kma *ccq_load_kma(char **files, int nfiles, const char *tmpl, unsigned minDe
 		K->len2[r] = m;
 		++r;
 	}
+	free(mat1);
 done:
 	for(int k = 0; k < nfiles; ++k) {
 		free(S[k].buf);

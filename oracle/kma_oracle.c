@@ -14,8 +14,12 @@
  *     stride although rows are 8 shorts, and without insertion rows it leaves
  *     len = rows + 1;
  *   - the metrics (matcmp.c:63-446) in their exact operation order, with int
- *     products that wrap (x86), nlinf comparing component 0 only, nln raising
+ *     products that wrap (x86), cos reading its 64-bit sums of wrapped squares
+ *     as signed (see m_cos), nlinf comparing component 0 only, nln raising
  *     the first difference without |.|, nc resetting its denominator;
+ *   - the row samples share ONE buffer (mat1), which FileBuffLoadMat never
+ *     clears: the row behind a sample's last one is a leftover of earlier
+ *     samples, and cmpMats can reach it (see load_mat1);
  *   - cmpMats (matcmp.c:448) and the inclusion rules of ltdMatrixThrd
  *     (ltdmatrixthrd.c:376-562): the first sample is checked over its rows
  *     with ref != '-', later ones over all rows.
@@ -115,16 +119,23 @@ static int next_row(const Blob *b, size_t *pos, Row *r) {
 /* ------------------------------------------------------------------ */
 static inline int imul(int a, int b) { return (int) ((unsigned) a * (unsigned) b); }
 
+/* coscmp (matcmp.c:420) squares ints into an unsigned long: a count of 46341 or
+ * more overflows the int product, which is undefined in C, so what happens is
+ * what the reference binary (oracle/Makefile's build) does, and that binary is
+ * the arbiter: the product wraps to 32 bits, is sign-extended into the 64-bit
+ * sum, and the sum goes to double as a SIGNED number.  A negative sum gives
+ * sqrt(negative) = NaN, d = NaN, and cmpMats' `0 <= d` drops the position; a
+ * zero sum returns -1 (dropped as well); non-negative sums are unaffected. */
 static double m_cos(const uint16_t *x, const uint16_t *y) {   /* matcmp.c:420 */
 	int a = x[0], b = y[0];
-	unsigned long c1 = (unsigned long) (long) imul(a, a), c2 = (unsigned long) (long) imul(b, b);
+	long c1 = imul(a, a), c2 = imul(b, b);
 	double d = imul(a, b);
 	for(int k = 1; k < 5; ++k) {
 		a = x[k];
 		b = y[k];
 		d += imul(a, b);
-		c1 += (unsigned long) (long) imul(a, a);
-		c2 += (unsigned long) (long) imul(b, b);
+		c1 += imul(a, a);
+		c2 += imul(b, b);
 	}
 	if(!c1 || !c2) return -1;
 	d = 1 - d / (sqrt((double) c1) * sqrt((double) c2));
@@ -322,31 +333,48 @@ static double metric(int m, unsigned lnorm, const uint16_t *x, const uint16_t *y
 /* row sample (mat1): 8 shorts per row, total in shorts 6-7            */
 /* ------------------------------------------------------------------ */
 typedef struct {
-	uint16_t *buf;     /* 8 * rows shorts */
+	uint16_t *buf;     /* 8 * cap shorts; ONE buffer for all row samples, like the reference's mat1 */
 	unsigned char *refs;
+	int cap;           /* rows allocated (> rows), zero-filled where never written */
 	int rows;          /* rows loaded (FileBuffLoadMat len) */
 	int len;           /* after stripMat */
 	unsigned nnucs;    /* FileBuffLoadMat nNucs: rows (any ref) with minDepth <= total */
 } Mat1;
 
+/* FileBuffLoadMat (matparse.c:213) into the shared buffer.  It overwrites rows
+ * 0 .. rows-1 and nothing else, so the rows behind them keep what EARLIER row
+ * samples left there (after their stripMat), or zero where nothing was ever
+ * written: the reference's initMat (dist.c:113) mallocs 16 MiB, which comes
+ * as fresh zero pages.  cmpMats reads one such row, see cmp_mats. */
 static int load_mat1(const Blob *b, size_t pos, unsigned minDepth, Mat1 *m) {
-	int cap = 1024;
 	Row r;
-	m->buf = malloc((size_t) cap * 16);
-	m->refs = malloc((size_t) cap + 1);
 	m->rows = 0;
 	m->nnucs = 0;
 	while(next_row(b, &pos, &r)) {
-		if(m->rows == cap) {
-			cap *= 2;
-			m->buf = realloc(m->buf, (size_t) cap * 16);
-			m->refs = realloc(m->refs, (size_t) cap + 1);
+		if(m->rows + 2 > m->cap) {
+			const int cap = m->cap ? 2 * m->cap : 1024;
+			uint16_t *nb = calloc((size_t) cap, 16);
+			unsigned char *nr = calloc((size_t) cap + 1, 1);
+			if(m->cap) {
+				memcpy(nb, m->buf, (size_t) m->cap * 16);
+				memcpy(nr, m->refs, (size_t) m->cap + 1);
+			}
+			free(m->buf);
+			free(m->refs);
+			m->buf = nb;
+			m->refs = nr;
+			m->cap = cap;
 		}
 		uint16_t *o = m->buf + 8 * (size_t) m->rows;
 		memcpy(o, r.c, 12);
 		memcpy(o + 6, &r.tot, 4);
 		m->refs[m->rows++] = r.ref;
 		if(minDepth <= r.tot) ++m->nnucs;
+	}
+	if(!m->cap) {
+		m->buf = calloc(1024, 16);
+		m->refs = calloc(1025, 1);
+		m->cap = 1024;
 	}
 	m->refs[m->rows] = 0;
 	return 0;
@@ -396,14 +424,11 @@ static double cmp_mats(const Mat1 *m1, const Blob *b, size_t pos, int metric_id,
 		if(minDepth <= r.tot) {
 			++nNucs;
 			uint32_t t1;
-			/* rows past the loaded ones (len = rows + 1 without insertions) are zero here */
-			if(c1 + 8 <= m1->buf + 8 * (size_t) m1->rows) {
-				memcpy(&t1, c1 + 6, 4);
-			} else {
-				t1 = 0;
-			}
-			static const uint16_t zero[6] = {0};
-			const uint16_t *x = (c1 + 8 <= m1->buf + 8 * (size_t) m1->rows) ? c1 : zero;
+			/* without insertion rows len = rows + 1, so a column sample of
+			 * exactly that many rows is compared, in its last row, with the
+			 * row behind the loaded ones: stale (load_mat1) */
+			const uint16_t *x = c1;
+			memcpy(&t1, c1 + 6, 4);
 			double d;
 			if(minDepth <= t1 && 0 <= (d = metric(metric_id, lnorm, x, r.c, (int) t1, (int) r.tot))) {
 				dist += d;
@@ -444,6 +469,7 @@ int orc_kma_dist(int nfiles, const char **files, const char *tmpl, int metric_id
 	Blob *blobs = calloc((size_t) nfiles, sizeof(Blob));
 	long *start = malloc((size_t) nfiles * sizeof(long));
 	int rc = 0, n = 0, i = 0;
+	Mat1 m1 = {0};
 	*n_out = 0;
 	for(int k = 0; k < nfiles; ++k) {
 		include[k] = 1;
@@ -488,12 +514,9 @@ int orc_kma_dist(int nfiles, const char **files, const char *tmpl, int metric_id
 			include[i] = 0;
 			continue;
 		}
-		Mat1 m1;
 		load_mat1(&blobs[i], (size_t) start[i], minDepth, &m1);
 		if(m1.nnucs < minLength || m1.nnucs < minCov * m1.rows) {
-			include[i] = 0;
-			free(m1.buf);
-			free(m1.refs);
+			include[i] = 0;   /* loaded, not stripped: its rows stay behind for later samples */
 			continue;
 		}
 		strip_mat1(&m1);
@@ -506,8 +529,6 @@ int orc_kma_dist(int nfiles, const char **files, const char *tmpl, int metric_id
 			                          minLength, minCov, &nt);
 			if(d == -2.0) {
 				rc = -2;   /* the reference exits(1) here (ltdmatrixthrd.c:337) */
-				free(m1.buf);
-				free(m1.refs);
 				goto done;
 			}
 			const int64_t f = (int64_t) row * (row - 1) / 2 + col;
@@ -515,12 +536,12 @@ int orc_kma_dist(int nfiles, const char **files, const char *tmpl, int metric_id
 			if(N) store(etype, bs, N, f, (double) nt);
 			++col;
 		}
-		free(m1.buf);
-		free(m1.refs);
 		++n;
 	}
 	*n_out = n;
 done:
+	free(m1.buf);
+	free(m1.refs);
 	for(int k = 0; k < nfiles; ++k) free(blobs[k].p);
 	free(blobs);
 	free(start);

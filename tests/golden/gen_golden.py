@@ -113,6 +113,95 @@ def kma_sample(path, templates, seed, depth=30, ins=0.0, gz=True, skip=(), trunc
             f.write("\n")
 
 
+KMA_EDGE = (0, 1, 2, 255, 256, 32767, 32768, 46340, 46341, 65535, 65536, 70000, 131071)
+
+
+def kma_adversarial(path, L, seed, profile, k=0, name="x", gz=True):
+    """Sample number `k` of an adversarial KMA count-matrix set over one
+    template of L positions (rows "ref A C G T N -" as kma_sample writes them).
+
+    profile "wrap":  counts 0..39 per slot; in about half the rows one of the
+                     five compared slots (A C G T -) holds a value of KMA_EDGE
+                     instead.  The reference's parser truncates counts to u16
+                     and keeps the full sum as the total, and its metrics
+                     multiply counts as 32-bit ints: 46341^2 is the first
+                     square that wraps negative.  At most one edge value per
+                     row, so one product wraps while l2's int sum of them
+                     stays in range.
+            "zero":  for -E 0.  Slots 0..2 (about half of them 0), about 20 %
+                     of the rows all zero and about 10 % with N only: zero
+                     totals, x/0 and 0/0 in every normalised metric.  Which
+                     rows these are is a property of the position, shared by
+                     the samples, with one row in 20 drawn again per sample:
+                     independent draws would leave under half the rows of a
+                     pair comparable and turn most cells to -1 (-C 50).
+            "plain": reads spread over the slots like kma_sample's, depth
+                     around gauss(20, 8), so part of the rows is under -E 15.
+                     The depth follows a per-position mean gauss(20, 8) that
+                     the samples share (+- gauss(0, 3) per sample), for the
+                     same reason.
+
+    Whatever the profile: every 5th sample has insertion rows (ref '-') after
+    about 2 % of its rows (stripMat's 7-short stride); samples 1, 7, 13, ..
+    begin with an insertion row and samples 4, 10, 16, .. end with one; samples
+    3, 7, 11, .. are 1, 2, 3, 1, .. rows short, which gives cmpMats' early -1
+    against a longer column sample wherever the stripped length falls under
+    that sample's."""
+    shared = random.Random(seed)            # what the samples have in common
+    ref = shared.choices("ACGT", k=L)
+    mean_depth = [shared.gauss(20, 8) for _ in range(L)]
+    row_kind = [shared.random() for _ in range(L)]
+    rng = random.Random(seed * 1000003 + 7919 * k + 1)
+    ins = 0.02 if k % 5 == 0 else 0.0
+    rows = L - (1 + (k // 4) % 3 if k % 4 == 3 else 0)
+
+    def ins_row():
+        c = [0] * 6
+        c[rng.randrange(4)] = rng.randrange(1, 40)
+        c[4] = rng.randrange(0, 10)
+        return "-\t" + "\t".join(map(str, c)) + "\n"
+
+    op = gzip.open if gz else open
+    with op(path, "wt") as f:
+        f.write(f"#{name}\n")
+        if k % 6 == 1:
+            f.write(ins_row())
+        for p in range(rows):
+            if profile == "wrap":
+                c = [rng.randrange(40) for _ in range(6)]
+                if rng.random() < 0.5:
+                    c[rng.choice((0, 1, 2, 3, 5))] = rng.choice(KMA_EDGE)
+            elif profile == "zero":
+                r = row_kind[p] if rng.random() < 0.95 else rng.random()
+                if r < 0.2:
+                    c = [0] * 6
+                elif r < 0.3:
+                    c = [0, 0, 0, 0, rng.randrange(1, 4), 0]
+                else:
+                    c = [rng.choice((0, 0, 0, 1, 1, 2)) for _ in range(6)]
+            elif profile == "plain":
+                c = [0] * 6
+                base = "ACGT".index(ref[p]) if rng.random() > 0.02 else rng.randrange(4)
+                for _ in range(max(0, int(rng.gauss(mean_depth[p], 3)))):
+                    r = rng.random()
+                    if r < 0.85:
+                        c[base] += 1
+                    elif r < 0.95:
+                        c[rng.randrange(4)] += 1
+                    elif r < 0.975:
+                        c[4] += 1
+                    else:
+                        c[5] += 1
+            else:
+                raise ValueError(profile)
+            f.write(ref[p] + "\t" + "\t".join(map(str, c)) + "\n")
+            if ins and p + 1 < rows and rng.random() < ins:
+                f.write(ins_row())
+        if k % 6 == 4:
+            f.write(ins_row())
+        f.write("\n")
+
+
 def run(args, out):
     p = subprocess.run([REF] + args, capture_output=True, check=True)
     with open(out, "wb") as f:
@@ -276,6 +365,27 @@ def main():
     case("ff_b_f3", ["dist", "-i"] + ffiles + ["-r", "gene_b", "-f", "3", "-n", "-"], "ff_b_f3.out", "fsafiles")
     case("ff_a_f3s", ["dist", "-i"] + ffiles + ["-r", "gene_a", "-f", "3", "-s", "10"], "ff_a_f3s.out", "fsafiles")
     case("ff_b_f3P", ["dist", "-i"] + ffiles + ["-r", "gene_b", "-f", "3", "-P", "6"], "ff_b_f3P.out", "fsafiles")
+
+    # (vii) adversarial KMA count matrices (kma_adversarial): counts at the u16
+    # and int32 edges under the default -E ("wrap"), zero totals under -E 0
+    # ("zero").  The binary is the arbiter of what wrapped products do: its
+    # coscmp reads the 64-bit sum of the wrapped squares as SIGNED, so a
+    # negative sum makes the norm NaN and drops the position.
+    for prof, extra in (("wrap", []), ("zero", ["-E", "0"])):
+        afiles = []
+        for k in range(9):
+            fn = f"adv_{prof}{k}.mat.gz"
+            kma_adversarial(fn, 400, seed=20, profile=prof, k=k)
+            afiles.append(fn)
+        base = ["dist", "-i"] + afiles + ["-r", "x"] + extra
+        for m in ("cos", "c", "l1", "l2", "linf", "chi2", "nchi2", "nc", "bc", "nbc", "nl1", "nl2", "nlinf", "l3",
+                  "nl3"):
+            case(f"kma_{prof}_{m}", base + ["-d", m], f"kma_{prof}_{m}.out", "kma")
+        for m in ("cos", "c", "nchi2", "l2"):
+            case(f"kma_{prof}_{m}_n", base + ["-d", m, "-n", "-"], f"kma_{prof}_{m}_n.out", "kma")
+            case(f"kma_{prof}_{m}_s", base + ["-d", m, "-s", "10"], f"kma_{prof}_{m}_s.out", "kma")
+            case(f"kma_{prof}_{m}_b", base + ["-d", m, "-b", "0.5"], f"kma_{prof}_{m}_b.out", "kma")
+            case(f"kma_{prof}_{m}_W", base + ["-d", m, "-W", "1000"], f"kma_{prof}_{m}_W.out", "kma")
 
     with open("golden.json", "w") as f:
         json.dump({"reference": "ccphylo 0.8.5 (oracle/_ref/ccphylo, built by oracle/Makefile)",

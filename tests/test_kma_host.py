@@ -22,15 +22,16 @@ def _i32(x):
 
 
 def _cos(x, y):
+    """coscmp as the reference binary runs it: products wrap to int32, the
+    sums of the squares are signed; a negative sum makes the norm NaN and the
+    position is dropped (reported here as -1, which cmpMats drops too)."""
     d = 0.0
     c1 = c2 = 0
     for k in range(5):
         d += _i32(int(x[k]) * int(y[k]))
-        c1 += _i32(int(x[k]) ** 2) % 2**64
-        c2 += _i32(int(y[k]) ** 2) % 2**64
-    c1 %= 2**64
-    c2 %= 2**64
-    if not c1 or not c2:
+        c1 += _i32(int(x[k]) ** 2)
+        c2 += _i32(int(y[k]) ** 2)
+    if c1 <= 0 or c2 <= 0:
         return -1.0
     d = 1 - d / (math.sqrt(float(c1)) * math.sqrt(float(c2)))
     return 0.0 if d < 0 else d
@@ -76,6 +77,42 @@ def test_loader_views_match_oracle(tmpl, metric):
     assert K["n"] == n and (K["include"] == inc).all()
     got = view_matrix(K, metric)
     assert np.array_equal(got, D)
+
+
+def _adv_files(profile, tmp_path_factory):
+    """The golden adversarial sets (wrap, zero); "plain" has no golden cases and
+    is written here, with the golden sets' shape and seed."""
+    if profile != "plain":
+        files = sorted(glob.glob(os.path.join(GOLDEN, f"adv_{profile}*.mat.gz")))
+        assert len(files) == 9
+        return files
+    import sys
+    sys.path.insert(0, GOLDEN)
+    from gen_golden import kma_adversarial
+    d = tmp_path_factory.mktemp("adv_plain")
+    files = [str(d / f"adv_plain{k}.mat.gz") for k in range(9)]
+    for k, f in enumerate(files):
+        kma_adversarial(f, 400, seed=20, profile="plain", k=k)
+    return files
+
+
+@pytest.mark.parametrize("metric", ["cos", "l1"])
+@pytest.mark.parametrize("profile,min_depth", [("wrap", 15), ("zero", 0), ("plain", 15)])
+def test_loader_views_match_oracle_adversarial(tmp_path_factory, profile, min_depth, metric):
+    """The same on the adversarial sets (gen_golden.kma_adversarial): counts at
+    the u16 / int32 edges, zero totals under min_depth 0, leading and trailing
+    insertion rows, and samples cut short -- one of them by a single row and
+    without insertion rows, whose last compared row is the leftover of the
+    samples loaded before it (kmamat.c, the replay of the reference's mat1)."""
+    import ccphylo_amd as cg
+    from oracle import pyoracle
+    files = _adv_files(profile, tmp_path_factory)
+    K = cg.native.load_kma(files, "x", min_depth=min_depth)
+    D, _, inc, n = pyoracle.kma_dist(files, "x", metric=metric, min_depth=min_depth)
+    assert K["n"] == n == 9 and (K["include"] == inc).all()
+    got = view_matrix(K, metric, min_depth=min_depth)
+    assert np.array_equal(got, D)
+    assert (D == -1).any() and (D >= 0).any()
 
 
 def test_loader_missing_file():
