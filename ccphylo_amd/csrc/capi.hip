@@ -244,8 +244,7 @@ done:
 int ccg_tree_dev(ccg_ctx *c, const ccg_tree_args *a, void *D, ccg_join *joins, int *njoins, int *final_n,
                  double *final_d, int64_t *stats) {
 	if(!c || !a || !D || !joins || !njoins || !final_n || !final_d) return CCG_EINVAL;
-	if(a->n < 3 || (a->method != CCG_TREE_NJ && a->method != CCG_TREE_DNJ && a->method != CCG_TREE_HNJ))
-		return CCG_EINVAL;
+	if(a->n < 3 || a->method < CCG_TREE_NJ || a->method > CCG_TREE_MN) return CCG_EINVAL;
 	if(a->etype != 8 && a->etype != 4 && a->etype != 2 && a->etype != 1) return CCG_EINVAL;
 	if((a->etype == 2 || a->etype == 1) && !(a->byteScale != 0)) return CCG_EINVAL;
 	CCG_CHECK(hipSetDevice(c->device));
@@ -270,7 +269,8 @@ int ccg_tree_dev_state(ccg_ctx *c, const ccg_tree_args *a, void *D, const ccg_dn
 int ccg_tree(ccg_ctx *c, const ccg_tree_args *a, const void *D, ccg_join *joins, int *njoins, int *final_n,
              double *final_d, int64_t *stats) {
 	if(!c || !a || !D) return CCG_EINVAL;
-	if(a->n < 3) return CCG_EINVAL;
+	if(a->n < 3 || a->method < CCG_TREE_NJ || a->method > CCG_TREE_MN) return CCG_EINVAL;
+	if(a->etype != 8 && a->etype != 4 && a->etype != 2 && a->etype != 1) return CCG_EINVAL;
 	CCG_CHECK(hipSetDevice(c->device));
 	size_t bytes = (size_t) a->n * (size_t) (a->n - 1) / 2 * (size_t) a->etype;
 	void *d = NULL;

@@ -159,6 +159,9 @@ struct TreeWork {
 };
 int ccg_tree_alloc(TreeWork *w, int n, hipStream_t st);
 size_t ccg_tree_bytes(int n);   // what ccg_tree_alloc allocates
+// CCG_TREE_UPGMA / CCG_TREE_CF / CCG_TREE_FF on a device LT (tree_linkage.hip)
+int ccg_tree_linkage_impl(ccg_ctx *ctx, const ccg_tree_args *a, void *Dd, ccg_join *joins, int *njoins, int *final_n,
+                          double *final_d, int64_t *stats);
 
 // ------------------------------------------------------------------ helpers
 __host__ __device__ static inline unsigned cdiv(long long a, long long b) { return (unsigned) ((a + b - 1) / b); }

@@ -1170,7 +1170,10 @@ __host__ __device__ __forceinline__ long long nj_blocks(int n) {
 	return nj_prefix(nseg, nb);
 }
 
-template <int ET, bool GEN>
+// MAXQ (-m mn, nj.c:297 initQ_MN): the same cells and Q, the maximum with
+// `max <= Q` from -DBL_MAX (the last maximal cell).  -Q is exact, so the block
+// keeps (-Q, f) under the same order and k_nj_join folds from DBL_MAX.
+template <int ET, bool GEN, bool MAXQ = false>
 __global__ __launch_bounds__(TB) void k_nj_argmin(const typename Elem<ET>::T *__restrict__ D, double bs, TreeBufs b,
                                                   int n) {
 	__shared__ double sq[TB / 64];
@@ -1192,7 +1195,7 @@ __global__ __launch_bounds__(TB) void k_nj_argmin(const typename Elem<ET>::T *__
 		sc[m] = b.sD[c];
 		nc[m] = GEN ? b.N[c] : n;
 	}
-	double bq = 1.0;
+	double bq = MAXQ ? DBL_MAX : 1.0;
 	long long bf = -1;
 	const int r0 = band * NJ_RB, r1 = r0 + NJ_RB < n ? r0 + NJ_RB : n;
 	constexpr int G = 4;   // rows per step: G*M loads in flight
@@ -1220,7 +1223,7 @@ __global__ __launch_bounds__(TB) void k_nj_argmin(const typename Elem<ET>::T *__
 			for(int m = 0; m < M; ++m) {
 				const int c = c0 + m * TB + (int) threadIdx.x;
 				const double d = Elem<ET>::get(v[g][m], bs);
-				const double q = qcrit(nr[g], nc[m], d, sr[g], sc[m]);
+				const double q = MAXQ ? -qcrit(nr[g], nc[m], d, sr[g], sc[m]) : qcrit(nr[g], nc[m], d, sr[g], sc[m]);
 				const long long f = base + c;
 				const bool take = r < r1 && c < r && 0 <= d && (q < bq || (q == bq && f > bf));
 				bq = take ? q : bq;
@@ -1954,9 +1957,10 @@ static int enqueue_iteration(hipStream_t st, typename Elem<ET>::T *D, double bs,
 		return (GEN ? 4 : 3) + xs;
 	}
 	const unsigned g = (unsigned) nj_blocks(n);
-	k_nj_argmin<ET, GEN><<<g, TB, 0, st>>>(D, bs, b, n);
+	if(method == CCG_TREE_MN) k_nj_argmin<ET, GEN, true><<<g, TB, 0, st>>>(D, bs, b, n);
+	else k_nj_argmin<ET, GEN><<<g, TB, 0, st>>>(D, bs, b, n);
 	kt.mark(CCG_K_ARGMIN);
-	k_nj_join<ET><<<gn, TB, 0, st>>>(D, bs, b, n, (int) g, general, 1.0);
+	k_nj_join<ET><<<gn, TB, 0, st>>>(D, bs, b, n, (int) g, general, method == CCG_TREE_MN ? DBL_MAX : 1.0);
 	if(GEN) k_update_general<ET><<<1, 1024, 0, st>>>(D, bs, b, n);
 	kt.mark(CCG_K_UPDATE);
 	if(xs) {
@@ -2358,6 +2362,13 @@ int ccg_selftest_row_sum_impl(ccg_ctx *ctx, const double *c, int n, double *out,
 
 int ccg_tree_impl(ccg_ctx *ctx, const ccg_tree_args *a, void *Dd, ccg_join *joins, int *njoins, int *final_n,
                   double *final_d, int64_t *stats, const ccg_dnj_state *sin, ccg_dnj_state *sout) {
+	if(a->method == CCG_TREE_UPGMA || a->method == CCG_TREE_CF || a->method == CCG_TREE_FF) {
+		if(sin || sout) return CCG_EINVAL;
+		return ccg_tree_linkage_impl(ctx, a, Dd, joins, njoins, final_n, final_d, stats);   // tree_linkage.hip
+	}
+	// NJ (and MN, its argmax form), DNJ and HNJ are the loops below; any other id must not fall through to NJ
+	if(a->method != CCG_TREE_NJ && a->method != CCG_TREE_DNJ && a->method != CCG_TREE_HNJ && a->method != CCG_TREE_MN)
+		return CCG_EINVAL;
 	switch(a->etype) {
 		case 8: return tree_run_t<8>(ctx, a, Dd, joins, njoins, final_n, final_d, stats, sin, sout);
 		case 4: return tree_run_t<4>(ctx, a, Dd, joins, njoins, final_n, final_d, stats, sin, sout);

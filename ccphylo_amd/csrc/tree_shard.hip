@@ -1045,9 +1045,17 @@ int ccg_rccl_open(ccg_ctx *ctx, const void *id, int rank, int world, ccg_coll *o
 	return CCG_OK;
 }
 
+// CCG_TREE_UPGMA / CF / FF / MN run on the single engine only
+static int shard_linkage_unsup(int method) {
+	if(method != CCG_TREE_UPGMA && method != CCG_TREE_CF && method != CCG_TREE_FF && method != CCG_TREE_MN) return CCG_OK;
+	ccg_set_last_msg("the sharded tree engine implements nj, dnj and hnj only (upgma, cf, ff and mn: one GPU)");
+	return CCG_EUNSUP;
+}
+
 int ccg_tree_shard_bytes(int64_t n, int etype, int method, int world, int64_t *device_bytes, int64_t *gather_bytes) {
 	if(!device_bytes || n < 3 || n > INT32_MAX - 512 || world < 1) return CCG_EINVAL;
 	if(etype != 8 && etype != 4 && etype != 2 && etype != 1) return CCG_EINVAL;
+	if(shard_linkage_unsup(method)) return CCG_EUNSUP;
 	if(method != CCG_TREE_NJ && method != CCG_TREE_DNJ && method != CCG_TREE_HNJ) return CCG_EINVAL;
 	const int n0 = (int) n;
 	*device_bytes = (int64_t) (method == CCG_TREE_DNJ ? ccg_shard_dnj_bytes(n0, world, etype)
@@ -1103,6 +1111,7 @@ static int shard_check(ccg_ctx *c, const ccg_tree_args *a, const ccg_coll *coll)
 
 int ccg_tree_shard_dev(ccg_ctx *c, const ccg_tree_args *a, const ccg_coll *coll, void *Dloc, ccg_join *joins,
                        int *njoins, int *final_n, double *final_d, int64_t *stats) {
+	if(a && shard_linkage_unsup(a->method)) return CCG_EUNSUP;
 	if(c && a && shard_world1_single(coll) && (!coll || coll->rank == 0)) {
 		if(!Dloc || !joins || !njoins || !final_n || !final_d) return CCG_EINVAL;
 		if(a->n < 3 || (a->method != CCG_TREE_NJ && a->method != CCG_TREE_DNJ && a->method != CCG_TREE_HNJ))
@@ -1136,6 +1145,7 @@ int ccg_tree_shard_dev(ccg_ctx *c, const ccg_tree_args *a, const ccg_coll *coll,
 
 int ccg_tree_shard(ccg_ctx *c, const ccg_tree_args *a, const ccg_coll *coll, const void *D, ccg_join *joins,
                    int *njoins, int *final_n, double *final_d, int64_t *stats) {
+	if(a && shard_linkage_unsup(a->method)) return CCG_EUNSUP;
 	int rc = c && a && shard_world1_single(coll) ? CCG_OK : shard_check(c, a, coll);
 	if(rc) return rc;
 	if(!D) return CCG_EINVAL;

@@ -28,6 +28,10 @@ ETYPES = {8: np.float64, 4: np.float32, 2: np.uint16, 1: np.uint8}
 CCG_TREE_NJ = 0
 CCG_TREE_DNJ = 1
 CCG_TREE_HNJ = 2
+CCG_TREE_UPGMA = 3
+CCG_TREE_CF = 4
+CCG_TREE_FF = 5
+CCG_TREE_MN = 6
 NKSTAT = 10
 KSTAT_NAMES = ["init", "dnj_select", "dnj_scan", "nj_argmin", "update", "dnj_requeue", "nj_pop", "dnj_find", "coll",
                "exact_sum"]
@@ -348,7 +352,7 @@ class Device:
 
     def tree(self, D, n, etype=8, byte_scale=1.0, method=CCG_TREE_DNJ, flags=0, exact=True, profile=False,
              max_joins=0):
-        """NJ/DNJ on a packed host LT (ccg_tree).  Returns (joins, final_n, final_d, stats)."""
+        """A tree (method: CCG_TREE_*) on a packed host LT (ccg_tree).  Returns (joins, final_n, final_d, stats)."""
         D = np.ascontiguousarray(D, dtype=ETYPES[etype])
         assert D.size == n * (n - 1) // 2
         return self._tree(self.lib.ccg_tree, D.ctypes.data, n, etype, byte_scale, method, flags, exact, profile,

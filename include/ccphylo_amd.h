@@ -179,12 +179,22 @@ typedef struct {
 #define CCG_TREE_NJ   0    /* -m nj  (nj.c:1560, the -t 1 semantics) */
 #define CCG_TREE_DNJ  1    /* -m dnj (dnj.c:985, default) */
 #define CCG_TREE_HNJ  2    /* -m hnj (hclust.c:1671: initHNJ, minQ, updateHNJ, HNJ_popArrange) */
+#define CCG_TREE_UPGMA 3   /* -m upgma (dnj.c:985 with initDmin, UPGMApair, updateUPGMA, UPGMA_popArrange) */
+#define CCG_TREE_CF    4   /* -m cf (hclust.c:1671 with initDmin, minQ, updateCF, UPGMA_popArrange);
+                              CCG_EUNSUP for a matrix with missing (negative) cells */
+#define CCG_TREE_FF    5   /* -m ff (as upgma, with updateFF hclust.c:884) */
+#define CCG_TREE_MN    6   /* -m mn (nj.c:1560 with initQ_MN nj.c:297, the -t 1 semantics) */
+/* Any other method id is CCG_EINVAL.  The four ids above run on the single
+ * engine (ccg_tree / ccg_tree_dev) only: the sharded entry points and
+ * ccg_tree_shard_bytes return CCG_EUNSUP for them, ccg_tree_dev_state stays
+ * DNJ only.  upgma, cf and ff always sum the new row of j in the reference's
+ * serial order: exact = 0 runs the exact path for them. */
 
 typedef struct {
 	int n;                 /* taxa (> 2) */
 	int etype;             /* 8, 4, 2, 1 */
 	double byteScale;
-	int method;            /* CCG_TREE_NJ / CCG_TREE_DNJ / CCG_TREE_HNJ */
+	int method;            /* CCG_TREE_* */
 	int flags;             /* tree -f: bit 2 = limbLengthNeg (nj.c:81) */
 	int exact;             /* 1: row sums of a join accumulated serially in the
 	                          reference order (bit-identical to the reference);
@@ -230,7 +240,8 @@ typedef struct {
  * On return *njoins joins were made; *final_n is the matrix size at exit
  * (2 normally; > 2 when the reference loop would stop early with pos == 0)
  * and *final_d the remaining pair's distance (D(1,0)) when *final_n == 2.
- * stats (may be NULL, 4 entries): [0] rows rescanned, [1] cells rescanned,
+ * stats (may be NULL, 4 entries): [0] rows rescanned, [1] cells rescanned
+ * (upgma / ff: the bounded rows UPGMApair's walk rescanned, dnj.c:246),
  * [2] kernel launches, [3] device time in microseconds. */
 int ccg_tree(ccg_ctx *ctx, const ccg_tree_args *a, const void *D,
              ccg_join *joins, int *njoins, int *final_n, double *final_d, int64_t *stats);
