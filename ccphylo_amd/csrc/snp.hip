@@ -687,6 +687,25 @@ __device__ __forceinline__ v8i_t fp4_xor_spread(const v8i_t &a, const v8i_t &b) 
 	return v;
 }
 
+// fp4_spread and fp4_xor_spread in two halves (dwords 0, 1: 4 / 2 VALU; dwords
+// 2, 3: 3 / 2 VALU), for k_snp_mfma3's one half per MFMA gap
+__device__ __forceinline__ void fp4_spread_half(v8i_t &v, uint32_t x, int hf) {
+	if(hf == 0) {
+		v[0] = (int) and_or(x << 3, 0x88888888u, 0x22222222u);
+		v[1] = (int) and_or(x << 2, 0x88888888u, 0x22222222u);
+		v[4] = v[5] = v[6] = v[7] = 0;
+	} else {
+		v[2] = (int) and_or(x << 1, 0x88888888u, 0x22222222u);
+		v[3] = (int) and_or(x, 0x88888888u, 0x22222222u);
+	}
+}
+
+__device__ __forceinline__ void fp4_xor_spread_half(v8i_t &v, const v8i_t &a, const v8i_t &b, int hf) {
+	if(hf == 0) v[4] = v[5] = v[6] = v[7] = 0;
+#pragma unroll
+	for(int q = 2 * hf; q < 2 * hf + 2; ++q) v[q] = (int) xor_or((uint32_t) a[q], (uint32_t) b[q], 0x22222222u);
+}
+
 template <int ET, bool SPLIT, bool BAND, int KCW = KC2>
 __global__ __launch_bounds__(256, 1) void k_snp_mfma2(const uint2 *__restrict__ P, int Wp, int n, long long t0,
                                                       long long items, int S, int Wk, double nFactor, double bs,
@@ -869,6 +888,31 @@ __global__ __launch_bounds__(256, 1) void k_snp_mfma2(const uint2 *__restrict__ 
 // wave.  Wave w stages slice w of both panels: 4 + 4 instructions per chunk.
 #define NST3 4
 #define KC3 8
+// CCG_DIST_STAMPS (the Makefile's `stamps` target, a diagnostic engine loaded
+// through CCPHYLO_AMD_ENGINE): k_snp_mfma3 stamps s_memtime around the parts
+// of each chunk of its main loop and sums the differences per part; lane 0 of
+// waves 0 and 3 store the sums to a buffer of their own, [item][wave][8]:
+// steps 0, 1, 2, step 3 up to the counted wait, the wait and the barrier, from
+// the barrier to the last DMA issue, the rest of step 3, the chunks summed.
+// The stamps fence the schedule (sched_barrier) and drain the LDS reads in
+// flight, so the shares are the record, not the run time.  The normal build
+// holds no stamp.
+#ifdef CCG_DIST_STAMPS
+#define ST3_SLOTS 8
+__device__ unsigned long long *ccg_dist_stamp_buf;
+__device__ long long ccg_dist_stamp_item0;
+#define ST3(K)                                                                              \
+	do {                                                                                    \
+		unsigned long long tn_;                                                             \
+		__builtin_amdgcn_sched_barrier(0);                                                  \
+		asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tn_)::"memory");         \
+		__builtin_amdgcn_sched_barrier(0);                                                  \
+		if((K) >= 0) stamp_sum[(K) < 0 ? 0 : (K)] += tn_ - stamp_prev;                      \
+		stamp_prev = tn_;                                                                   \
+	} while(0)
+#else
+#define ST3(K)
+#endif
 template <int ET, bool SPLIT, bool BAND>
 __global__ __launch_bounds__(256, 1) void k_snp_mfma3(const uint2 *__restrict__ P, int Wp, int n, long long t0,
                                                       long long items, int S, int Wk, double nFactor, double bs,
@@ -925,13 +969,15 @@ __global__ __launch_bounds__(256, 1) void k_snp_mfma3(const uint2 *__restrict__ 
 		             : "v"(src), "s"(lds)
 		             : "memory");
 	};
-	auto issue = [&](int c) {   // chunk c into stage c % NST3
-		const int st = c % NST3, w0 = c * KC3;
+	// this wave's slice of stage 0, panel A, in an SGPR: a piece's LDS address is scalar arithmetic on it
+	const unsigned lwave = (unsigned) __builtin_amdgcn_readfirstlane((int) (lbase + (unsigned) (wid * TILE2 * 16)));
+	auto issue1 = [&](int c, int i) {   // piece i of chunk c's 8 (rows 64 (i / 2) .. + 63 of panel i % 2) into stage c % NST3
+		const int st = c % NST3, w0 = c * KC3, q = i >> 1, p = i & 1;
+		glds((p ? srcB[q] : srcA[q]) + w0, lwave + (unsigned) ((((st * 2 + p) * NSL) * TILE2 + q * 64) * 16));
+	};
+	auto issue = [&](int c) {
 #pragma unroll
-		for(int q = 0; q < 4; ++q) {
-			glds(srcA[q] + w0, __builtin_amdgcn_readfirstlane(lbase + (unsigned) ((((st * 2 + 0) * NSL + wid) * TILE2 + q * 64) * 16)));
-			glds(srcB[q] + w0, __builtin_amdgcn_readfirstlane(lbase + (unsigned) ((((st * 2 + 1) * NSL + wid) * TILE2 + q * 64) * 16)));
-		}
+		for(int i = 0; i < 8; ++i) issue1(c, i);
 	};
 	const int wr = wid >> 1, wc = wid & 1;
 	const int h = lane >> 5, l32 = lane & 31;
@@ -955,15 +1001,15 @@ __global__ __launch_bounds__(256, 1) void k_snp_mfma3(const uint2 *__restrict__ 
 		asm volatile("" ::: "memory");
 	};
 	// step gs (64 positions): word 2 (gs % 4) + h of chunk gs / 4, rows ra0 + 32 x / rb0 + 32 x
-	auto rd = [&](int gs, uint2 (&a)[4], uint2 (&b)[4]) {
+	auto rd1 = [&](int gs, int p, uint2 (&v)[4]) {   // panel p (0: A, 1: B)
 		const int st = (gs >> 2) % NST3, sl = gs & 3;
-		const uint2 *Ac = (const uint2 *) &L[((st * 2 + 0) * NSL + sl) * TILE2];
-		const uint2 *Bc = (const uint2 *) &L[((st * 2 + 1) * NSL + sl) * TILE2];
+		const uint2 *Pc = (const uint2 *) &L[((st * 2 + p) * NSL + sl) * TILE2];
 #pragma unroll
-		for(int x = 0; x < 4; ++x) {
-			a[x] = Ac[(ra0 + 32 * x) * 2 + h];
-			b[x] = Bc[(rb0 + 32 * x) * 2 + h];
-		}
+		for(int x = 0; x < 4; ++x) v[x] = Pc[((p ? rb0 : ra0) + 32 * x) * 2 + h];
+	};
+	auto rd = [&](int gs, uint2 (&a)[4], uint2 (&b)[4]) {
+		rd1(gs, 0, a);
+		rd1(gs, 1, b);
 	};
 #define MF3(TA, TB, F, G)                                                                                         \
 	acc[TA][TB] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(F, G, acc[TA][TB], MFMA_FP4, MFMA_FP4, 0, MFMA_SCALE1, \
@@ -979,72 +1025,81 @@ __global__ __launch_bounds__(256, 1) void k_snp_mfma3(const uint2 *__restrict__ 
 		f0[x] = fp4_spread(a[x].x);
 		g0[x] = fp4_spread(b[x].x);
 	}
-	// Each component's 16 MFMAs carry the VALU work of the next component
-	// (one spread or xor per MFMA slot, pinned by sched_group_barrier), so the
-	// matrix pipe does not idle while a wave spreads (k_snp_mfma2: 16 MFMAs,
+#ifdef CCG_DIST_STAMPS
+	unsigned long long stamp_sum[ST3_SLOTS] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp_prev = 0;
+#endif
+	// Each component's 16 MFMAs carry the VALU work of the next component, so
+	// the matrix pipe does not idle while a wave spreads (k_snp_mfma2: 16 MFMAs,
 	// then the spreads; ~60% MFMA busy, profiles/r06_dist_clock.json):
 	//   comp 0 (f0, g0) + the spreads of lo (f1, g1)
-	//   comp 1 (f1, g1) + the xors (x0, y0) and the next step's LDS reads
+	//   comp 1 (f1, g1) + the xors (x0, y0), the next step's LDS reads, and in a
+	//                     chunk's last step the 8 DMA pieces of chunk c + NST3
 	//   comp 2 (x0, y0) + the next step's spreads of hi (f0, g0)
+	// The order is written out gap by gap and fenced: one MFMA, half a spread
+	// (4 or 3 VALU) or half an xor (2 VALU), then sched_barrier(0), so no gap
+	// holds more than 4 VALU (5 with a piece's address add) and the compiler
+	// cannot gather them (tools/micro/mfma_valu: up to 5 hide beside an MFMA).
+	// The operands are made in the order the next component reads them
+	// (ORD: f[0], g[0..3], f[1..3]), each at least 3 MFMAs before its reader.
 	// A chunk's last step waits for the next chunk (counted vmcnt + barrier)
-	// between comp 0 and comp 1, so its reads follow the barrier.
-	auto step = [&](auto SI, int gs, bool more, bool open) {   // SI: the step's place in its chunk (sync group ids)
-		constexpr int G0 = 3 * decltype(SI)::value;
+	// between comp 0 and comp 1, fenced on both sides, so that step's reads
+	// follow the barrier and every other MFMA-free instruction of the chunk
+	// open (the pieces and their M0 and address work) sits in a gap of comp 1.
+#define GAP3() __builtin_amdgcn_sched_barrier(0)
+	// OPEN: 0 = no chunk opens here; 1 = the next chunk opens, nothing left to
+	// issue (the last NST3 - 1 opens of a tile); 2 = it opens, chunk cn + NST3 - 1
+	// exists and 2 chunks stay in flight (vmcnt(16), known at compile time)
+	auto step = [&](auto OPEN, auto MORE, int gs) {
+		constexpr int open = decltype(OPEN)::value;
+		constexpr bool more = decltype(MORE)::value;
 		v8i_t f1[4], g1[4], x0[4], y0[4];
 #pragma unroll
 		for(int k = 0; k < 16; ++k) {
 			MF3(k >> 2, k & 3, f0[k >> 2], g0[k & 3]);
-			if(k < 8) {
-				if(k & 1) g1[k >> 1] = fp4_spread(b[k >> 1].y);
-				else f1[k >> 1] = fp4_spread(a[k >> 1].y);
+			const int j = k >> 1;   // operand j of ORD
+			if(j == 0 || j > 4) fp4_spread_half(f1[j ? j - 4 : 0], a[j ? j - 4 : 0].y, k & 1);
+			else fp4_spread_half(g1[j - 1], b[j - 1].y, k & 1);
+			GAP3();
+		}
+		const int cn = (gs + 1) >> 2;   // open: the next step opens chunk cn
+		if(open) {
+			ST3(3);
+			GAP3();
+			if(open == 2) {
+				asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+				asm volatile("" ::: "memory");
+				__builtin_amdgcn_s_barrier();
+				asm volatile("" ::: "memory");
+			} else {
+				land(cn);
 			}
-		}
-		// one spread (3 shifts, 4 bitop3) per MFMA on the first 8.  Measured at 50k x 5 Mbp: 4 VALU per slot
-		// on 14 slots was slower (6.43 against 6.26 s), 4 / 3 on all 16 slots (and 2 on component 1's) the
-		// same (5.56 against 5.54 s, headline data)
-#pragma unroll
-		for(int k = 0; k < 8; ++k) {
-			__builtin_amdgcn_sched_group_barrier(0x008, 1, G0);
-			__builtin_amdgcn_sched_group_barrier(0x002, 7, G0);
-		}
-		__builtin_amdgcn_sched_group_barrier(0x008, 8, G0);
-		if(open) {   // the next step opens chunk (gs + 1) / 4
-			const int cn = (gs + 1) >> 2;
-			land(cn);
-			if(cn + NST3 - 1 < nch) issue(cn + NST3 - 1);
+			GAP3();
+			ST3(4);
 		}
 		uint2 an[4], bn[4];
-		if(more) rd(gs + 1, an, bn);
 #pragma unroll
 		for(int k = 0; k < 16; ++k) {
 			MF3(k >> 2, k & 3, f1[k >> 2], g1[k & 3]);
-			if(k < 8) {
-				if(k & 1) y0[k >> 1] = fp4_xor_spread(g0[k >> 1], g1[k >> 1]);
-				else x0[k >> 1] = fp4_xor_spread(f0[k >> 1], f1[k >> 1]);
-			}
+			const int j = k >> 1;
+			if(j == 0 || j > 4) fp4_xor_spread_half(x0[j ? j - 4 : 0], f0[j ? j - 4 : 0], f1[j ? j - 4 : 0], k & 1);
+			else fp4_xor_spread_half(y0[j - 1], g0[j - 1], g1[j - 1], k & 1);
+			if(more && k == 0) rd1(gs + 1, 0, an);   // the next step's LDS reads, behind the barrier: A, then B
+			if(more && k == 1) rd1(gs + 1, 1, bn);
+			if(open == 2 && (k & 1)) issue1(cn + NST3 - 1, k >> 1);   // one piece in every other gap
+			GAP3();
 		}
-		if(more) __builtin_amdgcn_sched_group_barrier(0x100, 8, G0 + 1);   // the next step's 8 LDS reads first
-#pragma unroll
-		for(int k = 0; k < 8; ++k) {
-			__builtin_amdgcn_sched_group_barrier(0x008, 1, G0 + 1);
-			__builtin_amdgcn_sched_group_barrier(0x002, 4, G0 + 1);   // one xor (4 bitop3)
-		}
-		__builtin_amdgcn_sched_group_barrier(0x008, 8, G0 + 1);
+		if(open == 2) ST3(5);
 #pragma unroll
 		for(int k = 0; k < 16; ++k) {
 			MF3(k >> 2, k & 3, x0[k >> 2], y0[k & 3]);
-			if(more && k < 8) {
-				if(k & 1) g0[k >> 1] = fp4_spread(bn[k >> 1].x);
-				else f0[k >> 1] = fp4_spread(an[k >> 1].x);
+			if(more) {
+				const int j = k >> 1;
+				if(j == 0 || j > 4) fp4_spread_half(f0[j ? j - 4 : 0], an[j ? j - 4 : 0].x, k & 1);
+				else fp4_spread_half(g0[j - 1], bn[j - 1].x, k & 1);
 			}
+			GAP3();
 		}
 		if(more) {
-#pragma unroll
-			for(int k = 0; k < 8; ++k) {
-				__builtin_amdgcn_sched_group_barrier(0x008, 1, G0 + 2);
-				__builtin_amdgcn_sched_group_barrier(0x002, 7, G0 + 2);
-			}
-			__builtin_amdgcn_sched_group_barrier(0x008, 8, G0 + 2);
 #pragma unroll
 			for(int x = 0; x < 4; ++x) {
 				a[x] = an[x];
@@ -1052,20 +1107,45 @@ __global__ __launch_bounds__(256, 1) void k_snp_mfma3(const uint2 *__restrict__ 
 			}
 		}
 	};
-	for(int c = 0; c + 1 < nch; ++c) {   // every chunk but the last: 4 steps, the last one opens chunk c + 1
-		step(std::integral_constant<int, 0>(), 4 * c + 0, true, false);
-		step(std::integral_constant<int, 1>(), 4 * c + 1, true, false);
-		step(std::integral_constant<int, 2>(), 4 * c + 2, true, false);
-		step(std::integral_constant<int, 3>(), 4 * c + 3, true, true);
+	typedef std::integral_constant<int, 0> O0;
+	typedef std::integral_constant<int, 1> O1;
+	typedef std::integral_constant<int, 2> O2;
+	typedef std::true_type MT;
+	ST3(-1);
+	int c = 0;
+	for(; c + NST3 < nch; ++c) {   // 4 steps, the last one opens chunk c + 1 and issues chunk c + NST3
+		step(O0(), MT(), 4 * c + 0);
+		ST3(0);
+		step(O0(), MT(), 4 * c + 1);
+		ST3(1);
+		step(O0(), MT(), 4 * c + 2);
+		ST3(2);
+		step(O2(), MT(), 4 * c + 3);
+		ST3(6);
 	}
+	for(; c + 1 < nch; ++c) {   // the chunks with nothing left to issue, but the last
+		step(O0(), MT(), 4 * c + 0);
+		step(O0(), MT(), 4 * c + 1);
+		step(O0(), MT(), 4 * c + 2);
+		step(O1(), MT(), 4 * c + 3);
+	}
+#ifdef CCG_DIST_STAMPS
+	if(ccg_dist_stamp_buf && lane == 0 && (wid == 0 || wid == 3)) {
+		stamp_sum[7] = nch > NST3 ? nch - NST3 : 0;
+		unsigned long long *sb =
+		    ccg_dist_stamp_buf + ((t0 - ccg_dist_stamp_item0 + blockIdx.x) * 2 + (wid ? 1 : 0)) * ST3_SLOTS;
+		for(int k = 0; k < ST3_SLOTS; ++k) sb[k] = stamp_sum[k];
+	}
+#endif
 	{   // the last chunk
 		const int g = 4 * (nch - 1);
-		step(std::integral_constant<int, 0>(), g + 0, true, false);
-		step(std::integral_constant<int, 1>(), g + 1, true, false);
-		step(std::integral_constant<int, 2>(), g + 2, true, false);
-		step(std::integral_constant<int, 3>(), g + 3, false, false);
+		step(O0(), MT(), g + 0);
+		step(O0(), MT(), g + 1);
+		step(O0(), MT(), g + 2);
+		step(O0(), std::false_type(), g + 3);
 	}
 #undef MF3
+#undef GAP3
 	// epilogue: k_snp_mfma2's
 	const int L3 = 3 * 32 * Wl;
 #pragma unroll
@@ -1935,8 +2015,23 @@ static int snp_launch_mfma2(ccg_ctx *ctx, const ccg_snp_args *a, const void *pla
 	const long long batch = 1 << 16;
 	unsigned *cnt = NULL;
 	int rc = CCG_OK;
+#ifdef CCG_DIST_STAMPS
+	// the stamp sums of k_snp_mfma3, appended to the file CCG_DIST_STAMPS_OUT names (tools/dist_stamps.py reads it)
+	unsigned long long *d_st = NULL;
+	const char *sto = getenv("CCG_DIST_STAMPS_OUT");
+	const size_t stn = (size_t) (t_end - t_begin) * S * 2 * ST3_SLOTS;
+	const long long st_item0 = t_begin * S;
+#endif
 	// every failure below leaves through `out`, which frees d_pfx and cnt
 #define MF2_TRY(x) do { if((x) != hipSuccess) { rc = CCG_EHIP; goto out; } } while(0)
+#ifdef CCG_DIST_STAMPS
+	if(glds && sto) {
+		MF2_TRY(hipMalloc(&d_st, stn * sizeof(unsigned long long)));
+		MF2_TRY(hipMemsetAsync(d_st, 0, stn * sizeof(unsigned long long), ctx->stream));
+	}
+	MF2_TRY(hipMemcpyToSymbol(HIP_SYMBOL(ccg_dist_stamp_buf), &d_st, sizeof(d_st)));
+	MF2_TRY(hipMemcpyToSymbol(HIP_SYMBOL(ccg_dist_stamp_item0), &st_item0, sizeof(st_item0)));
+#endif
 	if(S > 1) {   // pair mode: dist counts, then n counts
 		const size_t cz = (size_t) (f1 - f0) * (PAIR ? 2 : 1) * sizeof(unsigned);
 		if(hipMalloc(&cnt, cz) != hipSuccess) {
@@ -2033,9 +2128,23 @@ static int snp_launch_mfma2(ccg_ctx *ctx, const ccg_snp_args *a, const void *pla
 		MF2_TRY(hipGetLastError());
 	}
 	MF2_TRY(hipStreamSynchronize(ctx->stream));
+#ifdef CCG_DIST_STAMPS
+	if(d_st) {
+		std::vector<unsigned long long> hs(stn);
+		MF2_TRY(hipMemcpy(hs.data(), d_st, stn * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+		FILE *sf = fopen(sto, "ab");
+		if(sf) {
+			fwrite(hs.data(), sizeof(unsigned long long), stn, sf);
+			fclose(sf);
+		}
+	}
+#endif
 out:
 #undef MF2_TRY
 	if(rc != CCG_OK) hipStreamSynchronize(ctx->stream);   // no launch may still read cnt / d_pfx
+#ifdef CCG_DIST_STAMPS
+	if(d_st) hipFree(d_st);
+#endif
 	if(cnt && hipFree(cnt) != hipSuccess && rc == CCG_OK) rc = CCG_EHIP;
 	if(d_pfx && hipFree(d_pfx) != hipSuccess && rc == CCG_OK) rc = CCG_EHIP;
 	return rc;
