@@ -10,6 +10,11 @@ struct Shard {
 	int rank, world;
 	__host__ __device__ __forceinline__ bool owns(long long r) const { return (int) ((r / SB) % world) == rank; }
 	__host__ __device__ __forceinline__ long long row(long long r) const { return off(r); }
+	// global row of the rank's L-th owned row (its rows in its own order)
+	__host__ __device__ __forceinline__ long long global_row(long long L) const {
+		const long long lb = L / SB;
+		return (lb * world + rank) * SB + (L - lb * SB);
+	}
 	// elements before owned row r in the rank's buffer: full owned bands below
 	// r's band (band g holds SB*SB*g + SB*(SB-1)/2 elements), then r's
 	// predecessors in its band

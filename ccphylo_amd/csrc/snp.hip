@@ -23,8 +23,15 @@
 //     is the register-staged form it replaced;
 //   - k_snp_tile / k_snp_tile_pair (CCG_DIST_MFMA=0): the popcount form
 //     above, VALU-integer-bound, 128x128 pair tiles, 8x8 pairs per thread in
-//     registers.
-// Both stage KC-word chunks of the two row panels through LDS.
+//     registers; k_snp_mfma / k_snp_mfma_pair (CCG_DIST_MFMA=1) are the first
+//     matrix-core form on the same 128x128 tiles.  These are the independent
+//     side of the bit-for-bit tests.
+// All stage chunks of a few words of the two row panels through LDS, and every
+// kernel is one template over SPLIT (split-K: word slices, exact u32 counts,
+// a finish kernel) and BAND (the A panel gathers one rank's owned rows of the
+// row-sharded layout, rows stored at Shard::off).  On the host, snp_launch
+// routes a matrix to snp_launch_mfma2 (256x256 tiles) or snp_launch_tile128;
+// both take their work from tile_range and their slices from plan_split.
 #include <cstring>
 #include <vector>
 #include <type_traits>
@@ -104,6 +111,24 @@ __device__ __forceinline__ void tile_ij(long long t, int &I, int &J) {
 	J = (int) (t - r * (r + 1) / 2);
 }
 
+// tile t of a rank's band list (tile_range): panel I = last with pfx[I] <= t, J = t - pfx[I]
+__device__ __forceinline__ void band_ij(const long long *__restrict__ pfx, int npanels, long long t, int &I, int &J) {
+	int lo = 0, hi = npanels - 1;
+	while(lo < hi) {
+		const int mid = (lo + hi + 1) >> 1;
+		if(pfx[mid] <= t) lo = mid; else hi = mid - 1;
+	}
+	I = lo;
+	J = (int) (t - pfx[lo]);
+}
+
+// the row a band A panel stages for the rank's L-th owned row (row l of panel
+// I: L = I * edge + l); owned rows past n stage row 0 and are never stored
+__device__ __forceinline__ long long band_row(const Shard &sh, long long L, int n) {
+	const long long r = sh.global_row(L);
+	return r < n ? r : 0;
+}
+
 // XCD-aware tile order: workgroups are dispatched round-robin over the 8
 // XCDs, so give XCD x a contiguous run of row-major tiles (tiles (I, J),
 // (I, J+1), ... share the I panel in that XCD's L2).  Bijective on [0, cnt).
@@ -117,20 +142,29 @@ __device__ __forceinline__ long long xcd_tile(long long b, long long cnt) {
 // from LDS, one barrier per chunk.  Work item = (tile, word slice): with
 // S > 1 slices (split-K, so small tile counts still fill the chip) the
 // partial counts are summed exactly with u32 atomics into `cnt` and
-// k_snp_finish writes D.
-template <int ET, bool SPLIT>
+// k_snp_finish writes D.  BAND: the tiles of one rank of the row-sharded
+// layout (ccg_shard.h): tile item / S of the rank's list (pfx), the A panel
+// gathers the rank's owned rows, so a rank computes only its own rows and
+// writes them at Shard::off, where ccg_tree_shard_dev reads them (SURVEY 8(d)
+// config 5); split-K counts are then indexed by the rank's local element.
+template <int ET, bool SPLIT, bool BAND>
 __global__ __launch_bounds__(256, 2) void k_snp_tile(const uint2 *__restrict__ P, int Wp, int n, long long t0,
                                                      long long items, int S, int Wk, double nFactor, double bs,
                                                      typename Elem<ET>::T *__restrict__ D, long long rowBegin,
-                                                     long long rowEnd, unsigned *__restrict__ cnt, long long cbase) {
+                                                     long long rowEnd, unsigned *__restrict__ cnt, long long cbase,
+                                                     const long long *__restrict__ pfx, int npanels, int rank,
+                                                     int world) {
 	__shared__ __attribute__((aligned(16))) uint2 As[2][KC * RS];
 	__shared__ __attribute__((aligned(16))) uint2 Bs[2][KC * RS];
 	int I, J;
 	const long long item = t0 + xcd_tile(blockIdx.x, items);
-	tile_ij(item / S, I, J);
+	if(BAND) band_ij(pfx, npanels, item / S, I, J);
+	else tile_ij(item / S, I, J);
+	const Shard sh{rank, world};
 	const int wb = (int) (item % S) * Wk, we = wb + Wk < Wp ? wb + Wk : Wp;
 	const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-	const uint2 *Ap = P + (size_t) I * TILE * Wp + wb;
+	// A-panel row l: Ap + arow(l) * Wp, the panel's own row l or (BAND) the rank's owned row I * TILE + l
+	const uint2 *Ap = P + (BAND ? 0 : (size_t) I * TILE * Wp) + wb;
 	const uint2 *Bp = P + (size_t) J * TILE * Wp + wb;
 	const int Wl = we - wb;   // words of this slice (a multiple of KC)
 	uint32_t acc[8][8];
@@ -140,10 +174,12 @@ __global__ __launch_bounds__(256, 2) void k_snp_tile(const uint2 *__restrict__ P
 		for(int c = 0; c < 8; ++c) acc[a][c] = 0;
 	// this thread's staging slots: rows e>>3, word pairs 2*(e&7), e = q*256 + tid
 	uint4 va[4], vb[4];
+	long long ar[4];
 #pragma unroll
 	for(int q = 0; q < 4; ++q) {
 		const int e = q * 256 + threadIdx.x, row = e >> 3, wp = e & 7;
-		va[q] = *(const uint4 *) (Ap + (size_t) row * Wp + 2 * wp);
+		ar[q] = BAND ? band_row(sh, (long long) I * TILE + row, n) : row;
+		va[q] = *(const uint4 *) (Ap + (size_t) ar[q] * Wp + 2 * wp);
 		vb[q] = *(const uint4 *) (Bp + (size_t) row * Wp + 2 * wp);
 	}
 #pragma unroll
@@ -162,7 +198,7 @@ __global__ __launch_bounds__(256, 2) void k_snp_tile(const uint2 *__restrict__ P
 #pragma unroll
 			for(int q = 0; q < 4; ++q) {
 				const int e = q * 256 + threadIdx.x, row = e >> 3, wp = e & 7;
-				va[q] = *(const uint4 *) (Ap + (size_t) row * Wp + w0 + KC + 2 * wp);
+				va[q] = *(const uint4 *) (Ap + (size_t) ar[q] * Wp + w0 + KC + 2 * wp);
 				vb[q] = *(const uint4 *) (Bp + (size_t) row * Wp + w0 + KC + 2 * wp);
 			}
 		}
@@ -202,9 +238,9 @@ __global__ __launch_bounds__(256, 2) void k_snp_tile(const uint2 *__restrict__ P
 	// epilogue: D[i][j] = nFactor * dist (fsacmpthrd.c:247-255), j < i only
 #pragma unroll
 	for(int a = 0; a < 8; ++a) {
-		long long i = (long long) I * TILE + 2 * ty + 32 * (a >> 1) + (a & 1);
-		if(i >= n || i < rowBegin || i >= rowEnd) continue;
-		long long base = tri(i);
+		const long long L = (long long) I * TILE + 2 * ty + 32 * (a >> 1) + (a & 1), i = BAND ? sh.global_row(L) : L;
+		if(i >= n || (!BAND && (i < rowBegin || i >= rowEnd))) continue;
+		const long long base = BAND ? sh.off(i) : tri(i);
 #pragma unroll
 		for(int c = 0; c < 8; ++c) {
 			long long j = (long long) J * TILE + 2 * tx + 32 * (c >> 1) + (c & 1);
@@ -271,20 +307,24 @@ __device__ __forceinline__ v8i_t fp4_spread(uint32_t x) {
 	return v;
 }
 
-template <int ET, bool SPLIT>
+template <int ET, bool SPLIT, bool BAND>
 __global__ __launch_bounds__(256, MFMA_BLOCKS) void k_snp_mfma(const uint2 *__restrict__ P, int Wp, int n, long long t0,
                                                      long long items, int S, int Wk, double nFactor, double bs,
                                                      typename Elem<ET>::T *__restrict__ D, long long rowBegin,
-                                                     long long rowEnd, unsigned *__restrict__ cnt, long long cbase) {
+                                                     long long rowEnd, unsigned *__restrict__ cnt, long long cbase,
+                                                     const long long *__restrict__ pfx, int npanels, int rank,
+                                                     int world) {
 	__shared__ __attribute__((aligned(16))) uint2 As[2][KCM * RS];
 	__shared__ __attribute__((aligned(16))) uint2 Bs[2][KCM * RS];
 	int I, J;
 	const long long item = t0 + xcd_tile(blockIdx.x, items);
-	tile_ij(item / S, I, J);
+	if(BAND) band_ij(pfx, npanels, item / S, I, J);
+	else tile_ij(item / S, I, J);
+	const Shard sh{rank, world};
 	const int wb = (int) (item % S) * Wk, we = wb + Wk < Wp ? wb + Wk : Wp;
 	const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
 	const int wr = wid >> 1, wc = wid & 1;   // this wave's 64x64 quarter
-	const uint2 *Ap = P + (size_t) I * TILE * Wp + wb;
+	const uint2 *Ap = P + (BAND ? 0 : (size_t) I * TILE * Wp) + wb;   // row l at Ap + arow(l) * Wp, as k_snp_tile
 	const uint2 *Bp = P + (size_t) J * TILE * Wp + wb;
 	const int Wl = we - wb;   // words of this slice (a multiple of KC)
 	v16f_t acc[2][2];
@@ -295,10 +335,12 @@ __global__ __launch_bounds__(256, MFMA_BLOCKS) void k_snp_mfma(const uint2 *__re
 #pragma unroll
 			for(int r = 0; r < 16; ++r) acc[a][c][r] = 0.0f;
 	uint4 va[QS], vb[QS];
+	long long ar[QS];
 #pragma unroll
 	for(int q = 0; q < QS; ++q) {
 		const int e = q * 256 + threadIdx.x, row = e / (KCM / 2), wp = e % (KCM / 2);
-		va[q] = *(const uint4 *) (Ap + (size_t) row * Wp + 2 * wp);
+		ar[q] = BAND ? band_row(sh, (long long) I * TILE + row, n) : row;
+		va[q] = *(const uint4 *) (Ap + (size_t) ar[q] * Wp + 2 * wp);
 		vb[q] = *(const uint4 *) (Bp + (size_t) row * Wp + 2 * wp);
 	}
 #pragma unroll
@@ -319,7 +361,7 @@ __global__ __launch_bounds__(256, MFMA_BLOCKS) void k_snp_mfma(const uint2 *__re
 #pragma unroll
 			for(int q = 0; q < QS; ++q) {
 				const int e = q * 256 + threadIdx.x, row = e / (KCM / 2), wp = e % (KCM / 2);
-				va[q] = *(const uint4 *) (Ap + (size_t) row * Wp + w0 + KCM + 2 * wp);
+				va[q] = *(const uint4 *) (Ap + (size_t) ar[q] * Wp + w0 + KCM + 2 * wp);
 				vb[q] = *(const uint4 *) (Bp + (size_t) row * Wp + w0 + KCM + 2 * wp);
 			}
 		}
@@ -369,9 +411,10 @@ __global__ __launch_bounds__(256, MFMA_BLOCKS) void k_snp_mfma(const uint2 *__re
 	for(int ta = 0; ta < 2; ++ta) {
 #pragma unroll
 		for(int r = 0; r < 16; ++r) {
-			const long long i = (long long) I * TILE + 64 * wr + 32 * ta + (r & 3) + 8 * (r >> 2) + 4 * h;
-			if(i >= n || i < rowBegin || i >= rowEnd) continue;
-			const long long base = tri(i);
+			const long long L = (long long) I * TILE + 64 * wr + 32 * ta + (r & 3) + 8 * (r >> 2) + 4 * h;
+			const long long i = BAND ? sh.global_row(L) : L;
+			if(i >= n || (!BAND && (i < rowBegin || i >= rowEnd))) continue;
+			const long long base = BAND ? sh.off(i) : tri(i);
 #pragma unroll
 			for(int tb = 0; tb < 2; ++tb) {
 				const long long j = (long long) J * TILE + 64 * wc + 32 * tb + l32;
@@ -389,245 +432,6 @@ __global__ __launch_bounds__(256, MFMA_BLOCKS) void k_snp_mfma(const uint2 *__re
 	}
 }
 
-// The same tiles for one rank of the row-sharded layout (ccg_shard.h): the A
-// panel gathers the rank's owned rows, so a rank computes only its own rows
-// and writes them where ccg_tree_shard_dev reads them.
-template <int ET>
-__global__ __launch_bounds__(256, 2) void k_snp_tile_band(const uint2 *__restrict__ P, int Wp, int n,
-                                                          const long long *__restrict__ pfx, int npanels, long long t0,
-                                                          long long items, double nFactor, double bs,
-                                                          typename Elem<ET>::T *__restrict__ Dloc, int rank, int world) {
-	__shared__ __attribute__((aligned(16))) uint2 As[2][KCM * RS];
-	__shared__ __attribute__((aligned(16))) uint2 Bs[2][KCM * RS];
-	// tile t of the rank's list: panel I = last with pfx[I] <= t, J = t - pfx[I]
-	const long long t = t0 + xcd_tile(blockIdx.x, items);
-	int lo = 0, hi = npanels - 1;
-	while(lo < hi) {
-		const int mid = (lo + hi + 1) >> 1;
-		if(pfx[mid] <= t) lo = mid; else hi = mid - 1;
-	}
-	const int I = lo, J = (int) (t - pfx[lo]);
-	const Shard sh{rank, world};
-	const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-	// A panel: the rank's owned rows I*TILE .. I*TILE+127 in its own order
-	// (band g = rows [SB g, SB g + SB) of rank g % world); rows past n read row 0
-	const auto arow = [&](int l) -> long long {
-		const long long L = (long long) I * TILE + l, lb = L / SB, g = lb * world + rank, r = g * SB + (L - lb * SB);
-		return r < n ? r : 0;
-	};
-	const uint2 *Bp = P + (size_t) J * TILE * Wp;
-	const int Wl = Wp;
-	uint32_t acc[8][8];
-#pragma unroll
-	for(int a = 0; a < 8; ++a)
-#pragma unroll
-		for(int c = 0; c < 8; ++c) acc[a][c] = 0;
-	// this thread's staging slots: rows e>>3, word pairs 2*(e&7), e = q*256 + tid
-	uint4 va[QS], vb[QS];
-#pragma unroll
-	for(int q = 0; q < 4; ++q) {
-		const int e = q * 256 + threadIdx.x, row = e >> 3, wp = e & 7;
-		va[q] = *(const uint4 *) (P + (size_t) arow(row) * Wp + 2 * wp);
-		vb[q] = *(const uint4 *) (Bp + (size_t) row * Wp + 2 * wp);
-	}
-#pragma unroll
-	for(int q = 0; q < 4; ++q) {
-		const int e = q * 256 + threadIdx.x, row = e >> 3, wp = e & 7;
-		As[0][(2 * wp) * RS + row] = make_uint2(va[q].x, va[q].y);
-		As[0][(2 * wp + 1) * RS + row] = make_uint2(va[q].z, va[q].w);
-		Bs[0][(2 * wp) * RS + row] = make_uint2(vb[q].x, vb[q].y);
-		Bs[0][(2 * wp + 1) * RS + row] = make_uint2(vb[q].z, vb[q].w);
-	}
-	__syncthreads();
-	int buf = 0;
-	for(int w0 = 0; w0 < Wl; w0 += KC, buf ^= 1) {
-		const bool more = w0 + KC < Wl;
-		if(more) {
-#pragma unroll
-			for(int q = 0; q < 4; ++q) {
-				const int e = q * 256 + threadIdx.x, row = e >> 3, wp = e & 7;
-				va[q] = *(const uint4 *) (P + (size_t) arow(row) * Wp + w0 + KC + 2 * wp);
-				vb[q] = *(const uint4 *) (Bp + (size_t) row * Wp + w0 + KC + 2 * wp);
-			}
-		}
-		const uint2 *Ac = As[buf], *Bc = Bs[buf];
-#pragma unroll 1
-		for(int w = 0; w < KC; ++w) {
-			uint4 a[4], b[4];
-#pragma unroll
-			for(int q = 0; q < 4; ++q) {
-				a[q] = *(const uint4 *) &Ac[w * RS + 2 * ty + 32 * q];
-				b[q] = *(const uint4 *) &Bc[w * RS + 2 * tx + 32 * q];
-			}
-#pragma unroll
-			for(int qa = 0; qa < 4; ++qa) {
-#pragma unroll
-				for(int qb = 0; qb < 4; ++qb) {
-					acc[2 * qa][2 * qb] += __popc(xor_or(a[qa].x, b[qb].x, a[qa].y ^ b[qb].y));
-					acc[2 * qa][2 * qb + 1] += __popc(xor_or(a[qa].x, b[qb].z, a[qa].y ^ b[qb].w));
-					acc[2 * qa + 1][2 * qb] += __popc(xor_or(a[qa].z, b[qb].x, a[qa].w ^ b[qb].y));
-					acc[2 * qa + 1][2 * qb + 1] += __popc(xor_or(a[qa].z, b[qb].z, a[qa].w ^ b[qb].w));
-				}
-			}
-		}
-		if(more) {
-			uint2 *An = As[buf ^ 1], *Bn = Bs[buf ^ 1];
-#pragma unroll
-			for(int q = 0; q < QS; ++q) {
-				const int e = q * 256 + threadIdx.x, row = e / (KCM / 2), wp = e % (KCM / 2);
-				An[(2 * wp) * RS + row] = make_uint2(va[q].x, va[q].y);
-				An[(2 * wp + 1) * RS + row] = make_uint2(va[q].z, va[q].w);
-				Bn[(2 * wp) * RS + row] = make_uint2(vb[q].x, vb[q].y);
-				Bn[(2 * wp + 1) * RS + row] = make_uint2(vb[q].z, vb[q].w);
-			}
-		}
-		__syncthreads();
-	}
-	// epilogue: the rank's row i at Shard::off(i) (fsacmpthrd.c:247-255 values)
-#pragma unroll
-	for(int a = 0; a < 8; ++a) {
-		const int l = 2 * ty + 32 * (a >> 1) + (a & 1);
-		const long long L = (long long) I * TILE + l, lb = L / SB, i = (lb * world + rank) * SB + (L - lb * SB);
-		if(i >= n) continue;
-		const long long base = sh.off(i);
-#pragma unroll
-		for(int c = 0; c < 8; ++c) {
-			long long j = (long long) J * TILE + 2 * tx + 32 * (c >> 1) + (c & 1);
-			if(j < i) Dloc[base + j] = Elem<ET>::put(nFactor * (double) acc[a][c], 0.5, bs);
-		}
-	}
-}
-
-// k_snp_mfma for one rank of the row-sharded layout (as k_snp_tile_band):
-// A panel = the rank's owned rows, rows stored at Shard::off(i).  SPLIT: word
-// slice item % S of Wk (< MFMA_KMAX) words, u32 counts added by local element
-// (k_snp_finish stores them), when the rank's tiles do not fill the chip or a
-// row exceeds the f32-exact slice length.
-template <int ET, bool SPLIT = false>
-__global__ __launch_bounds__(256, 2) void k_snp_mfma_band(const uint2 *__restrict__ P, int Wp, int n,
-                                                          const long long *__restrict__ pfx, int npanels, long long t0,
-                                                          long long items, double nFactor, double bs,
-                                                          typename Elem<ET>::T *__restrict__ Dloc, int rank, int world,
-                                                          int S = 1, int Wk = 0, unsigned *__restrict__ cnt = nullptr) {
-	__shared__ __attribute__((aligned(16))) uint2 As[2][KC * RS];
-	__shared__ __attribute__((aligned(16))) uint2 Bs[2][KC * RS];
-	const long long item = t0 + xcd_tile(blockIdx.x, items), t = SPLIT ? item / S : item;
-	// SPLIT: word slice item % S of Wk words (counts added into cnt by local element)
-	const int wb = SPLIT ? (int) (item % S) * Wk : 0;
-	int lo = 0, hi = npanels - 1;
-	while(lo < hi) {
-		const int mid = (lo + hi + 1) >> 1;
-		if(pfx[mid] <= t) lo = mid; else hi = mid - 1;
-	}
-	const int I = lo, J = (int) (t - pfx[lo]);
-	const Shard sh{rank, world};
-	const auto arow = [&](int l) -> long long {
-		const long long L = (long long) I * TILE + l, lb = L / SB, g = lb * world + rank, r = g * SB + (L - lb * SB);
-		return r < n ? r : 0;
-	};
-	const uint2 *Bp = P + (size_t) J * TILE * Wp + wb;
-	const int Wl = SPLIT ? (wb + Wk < Wp ? Wk : Wp - wb) : Wp;
-	const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-	const int wr = wid >> 1, wc = wid & 1;
-	v16f_t acc[2][2];
-#pragma unroll
-	for(int a = 0; a < 2; ++a)
-#pragma unroll
-		for(int c = 0; c < 2; ++c)
-#pragma unroll
-			for(int r = 0; r < 16; ++r) acc[a][c][r] = 0.0f;
-	uint4 va[4], vb[4];
-	long long ar[4];
-#pragma unroll
-	for(int q = 0; q < 4; ++q) {
-		const int e = q * 256 + threadIdx.x, row = e >> 3, wp = e & 7;
-		ar[q] = arow(row);
-		va[q] = *(const uint4 *) (P + (size_t) ar[q] * Wp + wb + 2 * wp);
-		vb[q] = *(const uint4 *) (Bp + (size_t) row * Wp + 2 * wp);
-	}
-#pragma unroll
-	for(int q = 0; q < 4; ++q) {
-		const int e = q * 256 + threadIdx.x, row = e >> 3, wp = e & 7;
-		As[0][(2 * wp) * RS + row] = make_uint2(va[q].x, va[q].y);
-		As[0][(2 * wp + 1) * RS + row] = make_uint2(va[q].z, va[q].w);
-		Bs[0][(2 * wp) * RS + row] = make_uint2(vb[q].x, vb[q].y);
-		Bs[0][(2 * wp + 1) * RS + row] = make_uint2(vb[q].z, vb[q].w);
-	}
-	__syncthreads();
-	const int h = lane >> 5, l32 = lane & 31;
-	const int ra0 = 64 * wr + l32, rb0 = 64 * wc + l32;
-	int buf = 0;
-	for(int w0 = 0; w0 < Wl; w0 += KC, buf ^= 1) {
-		const bool more = w0 + KC < Wl;
-		if(more) {
-#pragma unroll
-			for(int q = 0; q < 4; ++q) {
-				const int e = q * 256 + threadIdx.x, row = e >> 3, wp = e & 7;
-				va[q] = *(const uint4 *) (P + (size_t) ar[q] * Wp + wb + w0 + KC + 2 * wp);
-				vb[q] = *(const uint4 *) (Bp + (size_t) row * Wp + w0 + KC + 2 * wp);
-			}
-		}
-		const uint2 *Ac = As[buf], *Bc = Bs[buf];
-#pragma unroll 2
-		for(int s = 0; s < KC / 2; ++s) {
-			const int w = 2 * s + h;
-			uint2 a[2], b[2];
-#pragma unroll
-			for(int tt = 0; tt < 2; ++tt) {
-				a[tt] = Ac[w * RS + ra0 + 32 * tt];
-				b[tt] = Bc[w * RS + rb0 + 32 * tt];
-			}
-#pragma unroll
-			for(int comp = 0; comp < 3; ++comp) {
-				v8i_t fa[2], fb[2];
-#pragma unroll
-				for(int tt = 0; tt < 2; ++tt) {
-					fa[tt] = fp4_spread(comp == 0 ? a[tt].x : comp == 1 ? a[tt].y : a[tt].x ^ a[tt].y);
-					fb[tt] = fp4_spread(comp == 0 ? b[tt].x : comp == 1 ? b[tt].y : b[tt].x ^ b[tt].y);
-				}
-#pragma unroll
-				for(int ta = 0; ta < 2; ++ta)
-#pragma unroll
-					for(int tb = 0; tb < 2; ++tb)
-						acc[ta][tb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
-						    fa[ta], fb[tb], acc[ta][tb], MFMA_FP4, MFMA_FP4, 0, MFMA_SCALE1, 0, MFMA_SCALE1);
-			}
-		}
-		if(more) {
-			uint2 *An = As[buf ^ 1], *Bn = Bs[buf ^ 1];
-#pragma unroll
-			for(int q = 0; q < 4; ++q) {
-				const int e = q * 256 + threadIdx.x, row = e >> 3, wp = e & 7;
-				An[(2 * wp) * RS + row] = make_uint2(va[q].x, va[q].y);
-				An[(2 * wp + 1) * RS + row] = make_uint2(va[q].z, va[q].w);
-				Bn[(2 * wp) * RS + row] = make_uint2(vb[q].x, vb[q].y);
-				Bn[(2 * wp + 1) * RS + row] = make_uint2(vb[q].z, vb[q].w);
-			}
-		}
-		__syncthreads();
-	}
-	const int L3 = 3 * 32 * Wl;
-#pragma unroll
-	for(int ta = 0; ta < 2; ++ta) {
-#pragma unroll
-		for(int r = 0; r < 16; ++r) {
-			const int l = 64 * wr + 32 * ta + (r & 3) + 8 * (r >> 2) + 4 * h;
-			const long long L = (long long) I * TILE + l, lb = L / SB, i = (lb * world + rank) * SB + (L - lb * SB);
-			if(i >= n) continue;
-			const long long base = sh.off(i);
-#pragma unroll
-			for(int tb = 0; tb < 2; ++tb) {
-				const long long j = (long long) J * TILE + 64 * wc + 32 * tb + l32;
-				if(j < i) {
-					const unsigned d = (unsigned) ((L3 - (int) acc[ta][tb][r]) >> 2);
-					if(SPLIT) atomicAdd(&cnt[base + j], d);
-					else Dloc[base + j] = Elem<ET>::put(nFactor * (double) d, 0.5, bs);
-				}
-			}
-		}
-	}
-}
-
 // ------------------------------------------------------------------ MFMA, 256 x 256 tiles
 // k_snp_mfma2: the same exact MX-fp4 form on 256 x 256 pair tiles, one block of
 // 4 waves per CU, each wave 128 x 128 (4 x 4 MFMA tiles, 256 accumulator
@@ -638,7 +442,7 @@ __global__ __launch_bounds__(256, 2) void k_snp_mfma_band(const uint2 *__restric
 // xor, the 0x2 exponent bits cancel and are set again), so the VALU work per
 // MFMA drops about 3x and each staged panel byte feeds twice the position
 // pairs (half the panel traffic into the CUs).  BAND: the A panel gathers
-// one rank's owned rows of the band layout (k_snp_mfma_band), D indexed by
+// one rank's owned rows of the band layout (as k_snp_tile), D indexed by
 // Shard::off.  SPLIT: word slice item % S of Wk words, exact u32 counts.
 #define TILE2 256
 #define KC2 8                          // words per LDS chunk (the default; KC2L with CCG_DIST_KC=16)
@@ -1232,11 +1036,8 @@ __device__ __forceinline__ void pair_store(typename Elem<ET>::T *D, typename Ele
 // (uint4 {hi, lo, m, 0} per word): double-buffered KCP-word chunks of both
 // 128-row panels, XCD-contiguous tile order, and split-K over word slices when
 // the tiles do not fill the chip (exact u32 atomics of dist and n, then
-// k_snp_pair_finish applies the A7 epilogue).  BAND: one rank of the
-// row-sharded layout, as k_snp_tile_band (A panel = the rank's owned rows,
-// tile t of the rank's list found in pfx, rows stored at Shard::off(i), no
-// N); split-K counts are indexed by the rank's local element.
-template <int ET, bool SPLIT, bool BAND = false>
+// k_snp_pair_finish applies the A7 epilogue).  BAND as in k_snp_tile (no N).
+template <int ET, bool SPLIT, bool BAND>
 __global__ __launch_bounds__(256, 2) void k_snp_tile_pair(const uint4 *__restrict__ P, int Wp, int n, long long t0,
                                                           long long items, int S, int Wk, unsigned norm,
                                                           unsigned minLength, double bs,
@@ -1244,38 +1045,24 @@ __global__ __launch_bounds__(256, 2) void k_snp_tile_pair(const uint4 *__restric
                                                           typename Elem<ET>::T *__restrict__ Nm, long long rowBegin,
                                                           long long rowEnd, unsigned *__restrict__ cd,
                                                           unsigned *__restrict__ cn, long long cbase,
-                                                          const long long *__restrict__ pfx = nullptr, int npanels = 0,
-                                                          int rank = 0, int world = 1) {
+                                                          const long long *__restrict__ pfx, int npanels, int rank,
+                                                          int world) {
 	__shared__ __attribute__((aligned(16))) uint4 As[2][KCP * RSP];
 	__shared__ __attribute__((aligned(16))) uint4 Bs[2][KCP * RSP];
 	int I, J;
 	const long long item = t0 + xcd_tile(blockIdx.x, items);
-	if(BAND) {
-		const long long tile = item / S;
-		int lo = 0, hi = npanels - 1;
-		while(lo < hi) {
-			const int mid = (lo + hi + 1) >> 1;
-			if(pfx[mid] <= tile) lo = mid; else hi = mid - 1;
-		}
-		I = lo;
-		J = (int) (tile - pfx[lo]);
-	} else {
-		tile_ij(item / S, I, J);
-	}
-	// global row of A-panel row l (band: the rank's owned row I*TILE + l; rows
-	// past n read row 0)
-	const auto arow = [&](int l) -> long long {
-		const long long L = (long long) I * TILE + l;
-		if(!BAND) return L;
-		const long long lb = L / SB, r = (lb * world + rank) * SB + (L - lb * SB);
-		return r < n ? r : 0;
-	};
+	if(BAND) band_ij(pfx, npanels, item / S, I, J);
+	else tile_ij(item / S, I, J);
+	const Shard sh{rank, world};
 	const int wb = (int) (item % S) * Wk, we = wb + Wk < Wp ? wb + Wk : Wp;
 	const int Wl = we - wb;   // a multiple of KCP
 	const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
 	const uint4 *Aq[4];
 #pragma unroll
-	for(int q = 0; q < 4; ++q) Aq[q] = P + (size_t) arow((q * 256 + threadIdx.x) >> 3) * Wp + wb;
+	for(int q = 0; q < 4; ++q) {
+		const long long L = (long long) I * TILE + ((q * 256 + threadIdx.x) >> 3);
+		Aq[q] = P + (size_t) (BAND ? band_row(sh, L, n) : L) * Wp + wb;
+	}
 	const uint4 *Bp = P + (size_t) J * TILE * Wp + wb;
 	uint32_t ad[8][8], an[8][8];
 #pragma unroll
@@ -1345,17 +1132,9 @@ __global__ __launch_bounds__(256, 2) void k_snp_tile_pair(const uint4 *__restric
 #pragma unroll
 	for(int a = 0; a < 8; ++a) {
 		const int l = 2 * ty + 32 * (a >> 1) + (a & 1);
-		long long i = (long long) I * TILE + l;
-		long long base;
-		if(BAND) {
-			const long long lb = i / SB;
-			i = (lb * world + rank) * SB + (i - lb * SB);
-			if(i >= n) continue;
-			base = Shard{rank, world}.off(i);
-		} else {
-			if(i >= n || i < rowBegin || i >= rowEnd) continue;
-			base = tri(i);
-		}
+		const long long L = (long long) I * TILE + l, i = BAND ? sh.global_row(L) : L;
+		if(i >= n || (!BAND && (i < rowBegin || i >= rowEnd))) continue;
+		const long long base = BAND ? sh.off(i) : tri(i);
 #pragma unroll
 		for(int c = 0; c < 8; ++c) {
 			long long j = (long long) J * TILE + 2 * tx + 32 * (c >> 1) + (c & 1);
@@ -1397,7 +1176,7 @@ __device__ __forceinline__ v8i_t fp4_pair_comp(uint32_t hi, uint32_t lo, const u
 	return v;
 }
 
-template <int ET, bool SPLIT, bool BAND = false>
+template <int ET, bool SPLIT, bool BAND>
 __global__ __launch_bounds__(256, 2) void k_snp_mfma_pair(const uint4 *__restrict__ P, int Wp, int n, long long t0,
                                                           long long items, int S, int Wk, unsigned norm,
                                                           unsigned minLength, double bs,
@@ -1405,37 +1184,25 @@ __global__ __launch_bounds__(256, 2) void k_snp_mfma_pair(const uint4 *__restric
                                                           typename Elem<ET>::T *__restrict__ Nm, long long rowBegin,
                                                           long long rowEnd, unsigned *__restrict__ cd,
                                                           unsigned *__restrict__ cn, long long cbase,
-                                                          const long long *__restrict__ pfx = nullptr, int npanels = 0,
-                                                          int rank = 0, int world = 1) {
+                                                          const long long *__restrict__ pfx, int npanels, int rank,
+                                                          int world) {
 	__shared__ __attribute__((aligned(16))) uint4 As[2][KCP * RSP];
 	__shared__ __attribute__((aligned(16))) uint4 Bs[2][KCP * RSP];
 	int I, J;
 	const long long item = t0 + xcd_tile(blockIdx.x, items);
-	if(BAND) {   // as k_snp_tile_pair's band form
-		const long long tile = item / S;
-		int lo = 0, hi = npanels - 1;
-		while(lo < hi) {
-			const int mid = (lo + hi + 1) >> 1;
-			if(pfx[mid] <= tile) lo = mid; else hi = mid - 1;
-		}
-		I = lo;
-		J = (int) (tile - pfx[lo]);
-	} else {
-		tile_ij(item / S, I, J);
-	}
-	const auto arow = [&](int l) -> long long {
-		const long long L = (long long) I * TILE + l;
-		if(!BAND) return L;
-		const long long lb = L / SB, r = (lb * world + rank) * SB + (L - lb * SB);
-		return r < n ? r : 0;
-	};
+	if(BAND) band_ij(pfx, npanels, item / S, I, J);
+	else tile_ij(item / S, I, J);
+	const Shard sh{rank, world};
 	const int wb = (int) (item % S) * Wk, we = wb + Wk < Wp ? wb + Wk : Wp;
 	const int Wl = we - wb;   // a multiple of KCP
 	const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
 	const int wr = wid >> 1, wc = wid & 1;
 	const uint4 *Aq[4];
 #pragma unroll
-	for(int q = 0; q < 4; ++q) Aq[q] = P + (size_t) arow((q * 256 + threadIdx.x) >> 3) * Wp + wb;
+	for(int q = 0; q < 4; ++q) {
+		const long long L = (long long) I * TILE + ((q * 256 + threadIdx.x) >> 3);
+		Aq[q] = P + (size_t) (BAND ? band_row(sh, L, n) : L) * Wp + wb;
+	}
 	const uint4 *Bp = P + (size_t) J * TILE * Wp + wb;
 	v16f_t acc[2][2], accn[2][2];
 #pragma unroll
@@ -1523,17 +1290,10 @@ __global__ __launch_bounds__(256, 2) void k_snp_mfma_pair(const uint4 *__restric
 	for(int ta = 0; ta < 2; ++ta) {
 #pragma unroll
 		for(int r = 0; r < 16; ++r) {
-			long long i = (long long) I * TILE + 64 * wr + 32 * ta + (r & 3) + 8 * (r >> 2) + 4 * h;
-			long long base;
-			if(BAND) {
-				const long long lb = i / SB;
-				i = (lb * world + rank) * SB + (i - lb * SB);
-				if(i >= n) continue;
-				base = Shard{rank, world}.off(i);
-			} else {
-				if(i >= n || i < rowBegin || i >= rowEnd) continue;
-				base = tri(i);
-			}
+			const long long L = (long long) I * TILE + 64 * wr + 32 * ta + (r & 3) + 8 * (r >> 2) + 4 * h;
+			const long long i = BAND ? sh.global_row(L) : L;
+			if(i >= n || (!BAND && (i < rowBegin || i >= rowEnd))) continue;
+			const long long base = BAND ? sh.off(i) : tri(i);
 #pragma unroll
 			for(int tb = 0; tb < 2; ++tb) {
 				const long long j = (long long) J * TILE + 64 * wc + 32 * tb + l32;
@@ -1933,66 +1693,140 @@ __global__ __launch_bounds__(256) void k_snp_pair_proxi(const uint4 *__restrict_
 // ------------------------------------------------------------------ host
 static inline long long cdivll(long long a, long long b) { return (a + b - 1) / b; }
 
-// the non-pair dist kernel: 2 = k_snp_mfma2 (256 x 256 tiles, default),
-// 1 = k_snp_mfma (128 x 128), 0 = the VALU tiles (CCG_DIST_MFMA)
-static int dist_kernel_choice() {
-	const char *mf = getenv("CCG_DIST_MFMA");
-	return mf ? atoi(mf) : 2;
-}
-
-// k_snp_mfma2 over the LT rows [rb, re) (world == 0) or over one rank's rows
-// of the band layout (world > 0), with split-K over word slices when the
-// tiles do not fill the chip (one block per CU) or a row exceeds the
-// f32-exact slice, counts finished by k_snp_finish
-template <int ET, bool PAIR = false>
-static int snp_launch_mfma2(ccg_ctx *ctx, const ccg_snp_args *a, const void *planes, int Wp, double nFactor, void *D,
-                            long long rb, long long re, int rank, int world, void *N = NULL) {
-	typedef typename Elem<ET>::T T;
-	const long long n = a->n;
+// The work of one launch: tiles [t_begin, t_end) of edge `tile` and the output
+// elements [f0, f1) they fill.  world == 0: the tiles touching the LT rows
+// [rb, re).  world > 0: one rank's rows of the band layout in its own order,
+// as npanels panels of `tile` owned rows, each against the column tiles below
+// its last row (those with a cell j < i); pfx prefix-sums the tiles per panel,
+// so that a launch spans many panels and fills the chip (band_ij finds a tile
+// in its device copy d_pfx, which the launcher frees).  A rank that owns no
+// row has no panel.
+struct TileRange {
 	long long t_begin = 0, t_end = 0, f0 = 0, f1 = 0;
 	int npanels = 0;
+	std::vector<long long> pfx;   // lives until the launcher has synchronised the copy
 	long long *d_pfx = NULL;
-	if(world > 0) {
-		const long long nb = (n + SB - 1) / SB;
-		long long nloc = 0;   // owned rows below n
-		if(rank < nb) {
-			const long long owned = (nb - 1 - rank) / world + 1, last = (owned - 1) * world + rank;
-			nloc = (owned - 1) * SB + (n - last * SB < SB ? n - last * SB : SB);
-		}
-		npanels = (int) cdivll(nloc, TILE2);
-		if(npanels == 0) return CCG_OK;
-		std::vector<long long> pfx(npanels + 1, 0);
-		for(long long I = 0; I < npanels; ++I) {
-			const long long Lmax = (I + 1) * TILE2 - 1 < nloc - 1 ? (I + 1) * TILE2 - 1 : nloc - 1;
-			const long long lb = Lmax / SB, rmax = (lb * world + rank) * SB + (Lmax - lb * SB);
-			pfx[I + 1] = pfx[I] + cdivll(rmax, TILE2);
-		}
-		CCG_CHECK(hipMalloc(&d_pfx, (size_t) (npanels + 1) * sizeof(long long)));
-		if(hipMemcpyAsync(d_pfx, pfx.data(), (size_t) (npanels + 1) * sizeof(long long), hipMemcpyHostToDevice,
-		                  ctx->stream) != hipSuccess) {
-			hipFree(d_pfx);
-			return CCG_EHIP;
-		}
-		t_end = pfx[npanels];
-		f1 = ccg_shard_elems(n, rank, world);
-	} else {
-		const long long Ilo = rb / TILE2, Ihi = (re - 1) / TILE2;
-		t_begin = Ilo * (Ilo + 1) / 2;
-		t_end = (Ihi + 1) * (Ihi + 2) / 2;
-		f0 = tri(rb);
-		f1 = tri(re);
+};
+
+static int tile_range(ccg_ctx *ctx, long long n, long long rb, long long re, int rank, int world, int tile,
+                      TileRange *tr) {
+	if(world == 0) {
+		const long long Ilo = rb / tile, Ihi = (re - 1) / tile;
+		tr->t_begin = Ilo * (Ilo + 1) / 2;
+		tr->t_end = (Ihi + 1) * (Ihi + 2) / 2;
+		tr->f0 = tri(rb);
+		tr->f1 = tri(re);
+		return CCG_OK;
 	}
-	if(PAIR) {   // pair mode: items are tile column halves
-		t_begin *= 2;
-		t_end *= 2;
+	const Shard sh{rank, world};
+	const long long nb = cdivll(n, SB);
+	long long nloc = 0;   // owned rows below n
+	if(rank < nb) {
+		const long long owned = (nb - 1 - rank) / world + 1, last = (owned - 1) * world + rank;
+		nloc = (owned - 1) * SB + (n - last * SB < SB ? n - last * SB : SB);
 	}
-	const long long tiles = t_end - t_begin;
-	hipDeviceProp_t prop;
-	if(hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) {
-		hipFree(d_pfx);
+	const int np = (int) cdivll(nloc, tile);
+	if(np == 0) return CCG_OK;
+	tr->pfx.assign(np + 1, 0);
+	for(long long I = 0; I < np; ++I) {
+		const long long Lmax = ((I + 1) * tile < nloc ? (I + 1) * tile : nloc) - 1;   // the panel's last owned row
+		tr->pfx[I + 1] = tr->pfx[I] + cdivll(sh.global_row(Lmax), tile);
+	}
+	const size_t pb = (size_t) (np + 1) * sizeof(long long);
+	CCG_CHECK(hipMalloc(&tr->d_pfx, pb));
+	if(hipMemcpyAsync(tr->d_pfx, tr->pfx.data(), pb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+		hipFree(tr->d_pfx);
+		tr->d_pfx = NULL;
 		return CCG_EHIP;
 	}
-	const long long slots = prop.multiProcessorCount;   // one block per CU
+	tr->npanels = np;
+	tr->t_end = tr->pfx[np];
+	tr->f1 = ccg_shard_elems(n, rank, world);
+	return CCG_OK;
+}
+
+// Split-K: when `tiles` tiles do not fill the chip's `slots` resident blocks 16
+// times over (so the tail round of blocks is small), each tile's Wp words are
+// cut into S slices of Wk words, a multiple of the kernel's kc-word chunk; a
+// slice keeps >= 4 chunks.  kmax > 0: and Wk <= kmax (the f32-exact slice of
+// the MFMA forms), however many tiles there are.
+struct SplitPlan {
+	int S, Wk;
+};
+
+static SplitPlan plan_split(long long tiles, long long slots, int Wp, int kc, int kmax) {
+	const int chunks = Wp / kc;
+	int S = 1;
+	if(tiles < 16 * slots) {
+		S = (int) cdivll(16 * slots, tiles);
+		if(S > chunks / 4) S = chunks / 4;
+		if(S < 1) S = 1;
+	}
+	int Wk = (int) cdivll(chunks, S) * kc;
+	if(kmax && Wk > kmax) Wk = (kmax / kc) * kc;
+	return SplitPlan{(int) cdivll(Wp, Wk), Wk};
+}
+
+// the kernels' SPLIT and BAND template arguments from two runtime values:
+// f(std::bool_constant<SPLIT>(), std::bool_constant<BAND>())
+template <class F>
+static void with_split_band(bool split, bool band, F &&f) {
+	if(split && band) f(std::true_type(), std::true_type());
+	else if(split) f(std::true_type(), std::false_type());
+	else if(band) f(std::false_type(), std::true_type());
+	else f(std::false_type(), std::false_type());
+}
+
+// the zeroed u32 split-K counts of a launcher (pair mode: dist counts, then n counts)
+static int alloc_counts(ccg_ctx *ctx, size_t elems, unsigned **cnt) {
+	if(hipMalloc(cnt, elems * sizeof(unsigned)) != hipSuccess) {
+		*cnt = NULL;
+		return CCG_ENOMEM;
+	}
+	return hipMemsetAsync(*cnt, 0, elems * sizeof(unsigned), ctx->stream) == hipSuccess ? CCG_OK : CCG_EHIP;
+}
+
+// the split-K epilogue over the elements [f0, f1) (fsacmpthrd.c:247-255, resp. A7)
+template <int ET>
+static hipError_t launch_finish(ccg_ctx *ctx, const ccg_snp_args *a, const unsigned *cnt, long long f0, long long f1,
+                                double nFactor, typename Elem<ET>::T *D, typename Elem<ET>::T *N) {
+	const long long g = cdivll(f1 - f0, 256);
+	const unsigned grid = (unsigned) (g < 65536 ? g : 65536);
+	if(a->pair)
+		k_snp_pair_finish<ET><<<grid, 256, 0, ctx->stream>>>(cnt, cnt + (f1 - f0), f0, f1, a->norm, a->minLength,
+		                                                     a->byteScale, D, N);
+	else k_snp_finish<ET><<<grid, 256, 0, ctx->stream>>>(cnt, f0, f0, f1, nFactor, a->byteScale, D);
+	return hipGetLastError();
+}
+
+// a launcher's one exit: after an error no launch may still read cnt / d_pfx
+static int launch_exit(ccg_ctx *ctx, int rc, unsigned *cnt, long long *d_pfx) {
+	if(rc != CCG_OK) hipStreamSynchronize(ctx->stream);
+	if(cnt && hipFree(cnt) != hipSuccess && rc == CCG_OK) rc = CCG_EHIP;
+	if(d_pfx && hipFree(d_pfx) != hipSuccess && rc == CCG_OK) rc = CCG_EHIP;
+	return rc;
+}
+
+// every failure after a launcher's first allocation leaves through its `out`
+#define SNP_TRY(x) do { if((x) != hipSuccess) { rc = CCG_EHIP; goto out; } } while(0)
+
+// k_snp_mfma3 / k_snp_mfma2 / k_snp_mfma2_pair over the LT rows [rb, re)
+// (world == 0) or over one rank's rows of the band layout (world > 0, rb = 0,
+// re = n), with split-K over word slices when the tiles do not fill the chip
+// (one block per CU) or a row exceeds the f32-exact slice, counts finished by
+// k_snp_finish / k_snp_pair_finish
+template <int ET, bool PAIR>
+static int snp_launch_mfma2(ccg_ctx *ctx, const ccg_snp_args *a, const void *planes, int Wp, double nFactor, void *D,
+                            void *N, long long rb, long long re, int rank, int world) {
+	typedef typename Elem<ET>::T T;
+	const long long n = a->n;
+	hipDeviceProp_t prop;
+	CCG_CHECK(hipGetDeviceProperties(&prop, ctx->device));
+	TileRange tr;
+	const int trc = tile_range(ctx, n, rb, re, rank, world, TILE2, &tr);
+	if(trc != CCG_OK || (world > 0 && tr.npanels == 0)) return trc;
+	// pair mode: items are tile column halves
+	const long long t_begin = tr.t_begin * (PAIR ? 2 : 1), t_end = tr.t_end * (PAIR ? 2 : 1), f0 = tr.f0, f1 = tr.f1;
 	// words per LDS chunk (CCG_DIST_KC=16: half the barriers, 133 KB of LDS)
 	// and the tile order (CCG_DIST_ORDER=1: super-tiles, whole LT ranges from
 	// a super-row start only)
@@ -2002,17 +1836,10 @@ static int snp_launch_mfma2(ccg_ctx *ctx, const ccg_snp_args *a, const void *pla
 	const char *gle = getenv("CCG_DIST_GLDS");
 	const bool glds = !PAIR && !(gle && atoi(gle) == 0) && kc == KC3;
 	const int sorder = !PAIR && world == 0 && ore && atoi(ore) == 1 && (rb / TILE2) % 4 == 0;
-	const int chunks = Wp / kc;
-	int S = 1;
-	if(tiles < 16 * slots) {
-		S = (int) cdivll(16 * slots, tiles);
-		if(S > chunks / 4) S = chunks / 4;
-		if(S < 1) S = 1;
-	}
-	int Wk = (int) cdivll(chunks, S) * kc;
-	if(Wk > MFMA_KMAX) Wk = (MFMA_KMAX / kc) * kc;
-	S = (int) cdivll(Wp, Wk);
+	const SplitPlan plan = plan_split(t_end - t_begin, prop.multiProcessorCount, Wp, kc, MFMA_KMAX);   // one block per CU
+	const int S = plan.S, Wk = plan.Wk;
 	const long long batch = 1 << 16;
+	T *Nn = world > 0 ? NULL : (T *) N;
 	unsigned *cnt = NULL;
 	int rc = CCG_OK;
 #ifdef CCG_DIST_STAMPS
@@ -2021,117 +1848,44 @@ static int snp_launch_mfma2(ccg_ctx *ctx, const ccg_snp_args *a, const void *pla
 	const char *sto = getenv("CCG_DIST_STAMPS_OUT");
 	const size_t stn = (size_t) (t_end - t_begin) * S * 2 * ST3_SLOTS;
 	const long long st_item0 = t_begin * S;
-#endif
-	// every failure below leaves through `out`, which frees d_pfx and cnt
-#define MF2_TRY(x) do { if((x) != hipSuccess) { rc = CCG_EHIP; goto out; } } while(0)
-#ifdef CCG_DIST_STAMPS
 	if(glds && sto) {
-		MF2_TRY(hipMalloc(&d_st, stn * sizeof(unsigned long long)));
-		MF2_TRY(hipMemsetAsync(d_st, 0, stn * sizeof(unsigned long long), ctx->stream));
+		SNP_TRY(hipMalloc(&d_st, stn * sizeof(unsigned long long)));
+		SNP_TRY(hipMemsetAsync(d_st, 0, stn * sizeof(unsigned long long), ctx->stream));
 	}
-	MF2_TRY(hipMemcpyToSymbol(HIP_SYMBOL(ccg_dist_stamp_buf), &d_st, sizeof(d_st)));
-	MF2_TRY(hipMemcpyToSymbol(HIP_SYMBOL(ccg_dist_stamp_item0), &st_item0, sizeof(st_item0)));
+	SNP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(ccg_dist_stamp_buf), &d_st, sizeof(d_st)));
+	SNP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(ccg_dist_stamp_item0), &st_item0, sizeof(st_item0)));
 #endif
-	if(S > 1) {   // pair mode: dist counts, then n counts
-		const size_t cz = (size_t) (f1 - f0) * (PAIR ? 2 : 1) * sizeof(unsigned);
-		if(hipMalloc(&cnt, cz) != hipSuccess) {
-			cnt = NULL;
-			rc = CCG_ENOMEM;
-			goto out;
-		}
-		MF2_TRY(hipMemsetAsync(cnt, 0, cz, ctx->stream));
-	}
+	if(S > 1 && (rc = alloc_counts(ctx, (size_t) (f1 - f0) * (PAIR ? 2 : 1), &cnt)) != CCG_OK) goto out;
 	for(long long t = t_begin * S; t < t_end * S; t += batch) {
 		const long long items = t_end * S - t < batch ? t_end * S - t : batch;
-		const uint2 *pl = (const uint2 *) planes;
-		if(PAIR) {
-			typedef typename Elem<ET>::T T;
-			const uint4 *pp = (const uint4 *) planes;
-			unsigned *cn = cnt ? cnt + (f1 - f0) : NULL;
-			T *Nn = world > 0 ? NULL : (T *) N;
-			if(world > 0 && S > 1)
-				k_snp_mfma2_pair<ET, true, true><<<(unsigned) items, 256, 0, ctx->stream>>>(
-				    pp, Wp, (int) n, t, items, S, Wk, a->norm, a->minLength, a->byteScale, (T *) D, Nn, 0, n, cnt, cn, 0,
-				    d_pfx, npanels, rank, world);
-			else if(world > 0)
-				k_snp_mfma2_pair<ET, false, true><<<(unsigned) items, 256, 0, ctx->stream>>>(
-				    pp, Wp, (int) n, t, items, 1, Wp, a->norm, a->minLength, a->byteScale, (T *) D, Nn, 0, n, cnt, cn, 0,
-				    d_pfx, npanels, rank, world);
-			else if(S > 1)
-				k_snp_mfma2_pair<ET, true, false><<<(unsigned) items, 256, 0, ctx->stream>>>(
-				    pp, Wp, (int) n, t, items, S, Wk, a->norm, a->minLength, a->byteScale, (T *) D, Nn, rb, re, cnt, cn,
-				    f0, NULL, 0, 0, 1);
+		with_split_band(S > 1, world > 0, [&](auto SP, auto BD) {
+			constexpr bool sp = decltype(SP)::value, bd = decltype(BD)::value;
+			const uint2 *pl = (const uint2 *) planes;
+			if(PAIR)
+				k_snp_mfma2_pair<ET, sp, bd><<<(unsigned) items, 256, 0, ctx->stream>>>(
+				    (const uint4 *) planes, Wp, (int) n, t, items, S, Wk, a->norm, a->minLength, a->byteScale, (T *) D, Nn,
+				    rb, re, cnt, cnt ? cnt + (f1 - f0) : NULL, f0, tr.d_pfx, tr.npanels, rank, world);
+			else if(glds)   // KC3-word chunks, LDS-DMA staged
+				k_snp_mfma3<ET, sp, bd><<<(unsigned) items, 256, 0, ctx->stream>>>(
+				    pl, Wp, (int) n, t, items, S, Wk, nFactor, a->byteScale, (T *) D, rb, re, cnt, f0, tr.d_pfx, tr.npanels,
+				    rank, world, sorder);
+			else if(kc == KC2L)
+				k_snp_mfma2<ET, sp, bd, KC2L><<<(unsigned) items, 256, 0, ctx->stream>>>(
+				    pl, Wp, (int) n, t, items, S, Wk, nFactor, a->byteScale, (T *) D, rb, re, cnt, f0, tr.d_pfx, tr.npanels,
+				    rank, world, sorder);
 			else
-				k_snp_mfma2_pair<ET, false, false><<<(unsigned) items, 256, 0, ctx->stream>>>(
-				    pp, Wp, (int) n, t, items, 1, Wp, a->norm, a->minLength, a->byteScale, (T *) D, Nn, rb, re, cnt, cn,
-				    f0, NULL, 0, 0, 1);
-			MF2_TRY(hipGetLastError());
-			continue;
-		}
-#define MF2_LAUNCH(KCV)                                                                                              \
-	if(world > 0) {                                                                                                  \
-		if(S > 1)                                                                                                    \
-			k_snp_mfma2<ET, true, true, KCV><<<(unsigned) items, 256, 0, ctx->stream>>>(                             \
-			    pl, Wp, (int) n, t, items, S, Wk, nFactor, a->byteScale, (T *) D, 0, n, cnt, 0, d_pfx, npanels, rank,  \
-			    world, 0);                                                                                           \
-		else                                                                                                         \
-			k_snp_mfma2<ET, false, true, KCV><<<(unsigned) items, 256, 0, ctx->stream>>>(                            \
-			    pl, Wp, (int) n, t, items, 1, Wp, nFactor, a->byteScale, (T *) D, 0, n, cnt, 0, d_pfx, npanels, rank,  \
-			    world, 0);                                                                                           \
-	} else {                                                                                                         \
-		if(S > 1)                                                                                                    \
-			k_snp_mfma2<ET, true, false, KCV><<<(unsigned) items, 256, 0, ctx->stream>>>(                            \
-			    pl, Wp, (int) n, t, items, S, Wk, nFactor, a->byteScale, (T *) D, rb, re, cnt, f0, NULL, 0, 0, 1,       \
-			    sorder);                                                                                             \
-		else                                                                                                         \
-			k_snp_mfma2<ET, false, false, KCV><<<(unsigned) items, 256, 0, ctx->stream>>>(                           \
-			    pl, Wp, (int) n, t, items, 1, Wp, nFactor, a->byteScale, (T *) D, rb, re, cnt, f0, NULL, 0, 0, 1,       \
-			    sorder);                                                                                             \
+				k_snp_mfma2<ET, sp, bd, KC2><<<(unsigned) items, 256, 0, ctx->stream>>>(
+				    pl, Wp, (int) n, t, items, S, Wk, nFactor, a->byteScale, (T *) D, rb, re, cnt, f0, tr.d_pfx, tr.npanels,
+				    rank, world, sorder);
+		});
+		SNP_TRY(hipGetLastError());
 	}
-		if(glds) {   // k_snp_mfma3 (KC3-word chunks, LDS-DMA staged)
-			if(world > 0) {
-				if(S > 1)
-					k_snp_mfma3<ET, true, true><<<(unsigned) items, 256, 0, ctx->stream>>>(
-					    pl, Wp, (int) n, t, items, S, Wk, nFactor, a->byteScale, (T *) D, 0, n, cnt, 0, d_pfx, npanels,
-					    rank, world, 0);
-				else
-					k_snp_mfma3<ET, false, true><<<(unsigned) items, 256, 0, ctx->stream>>>(
-					    pl, Wp, (int) n, t, items, 1, Wp, nFactor, a->byteScale, (T *) D, 0, n, cnt, 0, d_pfx, npanels,
-					    rank, world, 0);
-			} else {
-				if(S > 1)
-					k_snp_mfma3<ET, true, false><<<(unsigned) items, 256, 0, ctx->stream>>>(
-					    pl, Wp, (int) n, t, items, S, Wk, nFactor, a->byteScale, (T *) D, rb, re, cnt, f0, NULL, 0, 0, 1,
-					    sorder);
-				else
-					k_snp_mfma3<ET, false, false><<<(unsigned) items, 256, 0, ctx->stream>>>(
-					    pl, Wp, (int) n, t, items, 1, Wp, nFactor, a->byteScale, (T *) D, rb, re, cnt, f0, NULL, 0, 0, 1,
-					    sorder);
-			}
-		} else if(kc == KC2L) {
-			MF2_LAUNCH(KC2L)
-		} else {
-			MF2_LAUNCH(KC2)
-		}
-#undef MF2_LAUNCH
-		MF2_TRY(hipGetLastError());
-	}
-	if(S > 1) {
-		const long long g = cdivll(f1 - f0, 256);
-		if(PAIR)
-			k_snp_pair_finish<ET><<<(unsigned) (g < 65536 ? g : 65536), 256, 0, ctx->stream>>>(
-			    cnt, cnt + (f1 - f0), f0, f1, a->norm, a->minLength, a->byteScale, (T *) D,
-			    world > 0 ? (T *) NULL : (T *) N);
-		else
-			k_snp_finish<ET><<<(unsigned) (g < 65536 ? g : 65536), 256, 0, ctx->stream>>>(cnt, f0, f0, f1, nFactor,
-			                                                                                a->byteScale, (T *) D);
-		MF2_TRY(hipGetLastError());
-	}
-	MF2_TRY(hipStreamSynchronize(ctx->stream));
+	if(S > 1) SNP_TRY(launch_finish<ET>(ctx, a, cnt, f0, f1, nFactor, (T *) D, Nn));
+	SNP_TRY(hipStreamSynchronize(ctx->stream));
 #ifdef CCG_DIST_STAMPS
 	if(d_st) {
 		std::vector<unsigned long long> hs(stn);
-		MF2_TRY(hipMemcpy(hs.data(), d_st, stn * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+		SNP_TRY(hipMemcpy(hs.data(), d_st, stn * sizeof(unsigned long long), hipMemcpyDeviceToHost));
 		FILE *sf = fopen(sto, "ab");
 		if(sf) {
 			fwrite(hs.data(), sizeof(unsigned long long), stn, sf);
@@ -2140,325 +1894,116 @@ static int snp_launch_mfma2(ccg_ctx *ctx, const ccg_snp_args *a, const void *pla
 	}
 #endif
 out:
-#undef MF2_TRY
-	if(rc != CCG_OK) hipStreamSynchronize(ctx->stream);   // no launch may still read cnt / d_pfx
 #ifdef CCG_DIST_STAMPS
 	if(d_st) hipFree(d_st);
 #endif
-	if(cnt && hipFree(cnt) != hipSuccess && rc == CCG_OK) rc = CCG_EHIP;
-	if(d_pfx && hipFree(d_pfx) != hipSuccess && rc == CCG_OK) rc = CCG_EHIP;
-	return rc;
+	return launch_exit(ctx, rc, cnt, tr.d_pfx);
 }
 
+// The 128 x 128 tile kernels, in snp_launch_mfma2's shape: k_snp_mfma /
+// k_snp_mfma_pair (mfma) or the VALU tiles k_snp_tile / k_snp_tile_pair, two
+// blocks per CU in the plan.  k_snp_mfma is planned in k_snp_tile's KC-word
+// chunks (it stages KCM-word ones) with its slices clamped to the f32-exact
+// length; pair mode is not clamped, and k_snp_mfma_pair gives way to the VALU
+// pair tiles when a slice is longer than that.
 template <int ET>
-static int snp_launch(ccg_ctx *ctx, const ccg_snp_args *a, const void *planes, int Wp, double nFactor, void *D, void *N,
-                      long long rb, long long re) {
-	typedef typename Elem<ET>::T T;
-	long long Ilo = rb / TILE, Ihi = (re - 1) / TILE;   // tile rows touching [rb, re)
-	long long t_begin = Ilo * (Ilo + 1) / 2, t_end = (Ihi + 1) * (Ihi + 2) / 2;
-	const long long batch = 1 << 14;
-	if(a->pair && a->proxi) {
-		const long long f0 = tri(rb), f1 = tri(re), g = cdivll(f1 - f0, 4);
-		const int W32 = (a->len + 31) / 32;
-		if(f1 > f0) {
-			k_snp_pair_proxi<ET><<<(unsigned) (g < 16384 ? g : 16384), 256, 0, ctx->stream>>>(
-			    (const uint4 *) planes, Wp, W32, a->len, (int) a->proxi, f0, f1, a->norm, a->minLength, a->byteScale,
-			    (T *) D, (T *) N);
-			CCG_CHECK(hipGetLastError());
-		}
-		return CCG_OK;
-	}
-	// split-K: enough (tile, slice) items that the tail round of resident
-	// blocks (2 per CU) is small; each slice keeps >= 4 chunks
-	hipDeviceProp_t prop;
-	CCG_CHECK(hipGetDeviceProperties(&prop, ctx->device));
-	const long long slots = 2LL * prop.multiProcessorCount;
-	const long long tiles = t_end - t_begin;
-	const int kc = a->pair ? KCP : KC;
-	const int chunks = Wp / kc;
-	int S = 1;
-	if(tiles < 16 * slots) {
-		S = (int) cdivll(16 * slots, tiles);
-		if(S > chunks / 4) S = chunks / 4;
-		if(S < 1) S = 1;
-	}
-	const int Wk = (int) cdivll(chunks, S) * kc;
-	S = (int) cdivll(Wp, Wk);
-	const long long f0 = tri(rb), f1 = tri(re);
-	const long long i_begin = t_begin * S, i_end = t_end * S;
-	if(a->pair && dist_kernel_choice() == 2)   // k_snp_mfma2_pair (CCG_DIST_MFMA=1: k_snp_mfma_pair, 0: VALU tiles)
-		return snp_launch_mfma2<ET, true>(ctx, a, planes, Wp, nFactor, D, rb, re, 0, 0, N);
-	if(a->pair) {
-		unsigned *cd = NULL, *cn = NULL;
-		if(S > 1) {
-			CCG_CHECK(hipMalloc(&cd, (size_t) (f1 - f0) * 2 * sizeof(unsigned)));
-			cn = cd + (f1 - f0);
-			CCG_CHECK(hipMemsetAsync(cd, 0, (size_t) (f1 - f0) * 2 * sizeof(unsigned), ctx->stream));
-		}
-		// the MFMA form (default; CCG_DIST_MFMA=0: VALU tiles) while a slice is f32-exact
-		const char *mfp = getenv("CCG_DIST_MFMA");
-		const bool pmfma = (mfp ? atoi(mfp) : 1) && Wk < MFMA_KMAX;
-		for(long long t = i_begin; t < i_end; t += batch) {
-			long long items = i_end - t < batch ? i_end - t : batch;
-			if(pmfma) {
-				if(S > 1)
-					k_snp_mfma_pair<ET, true><<<(unsigned) items, 256, 0, ctx->stream>>>(
-					    (const uint4 *) planes, Wp, a->n, t, items, S, Wk, a->norm, a->minLength, a->byteScale, (T *) D,
-					    (T *) N, rb, re, cd, cn, f0);
-				else
-					k_snp_mfma_pair<ET, false><<<(unsigned) items, 256, 0, ctx->stream>>>(
-					    (const uint4 *) planes, Wp, a->n, t, items, 1, Wp, a->norm, a->minLength, a->byteScale, (T *) D,
-					    (T *) N, rb, re, cd, cn, f0);
-			} else if(S > 1) {
-				k_snp_tile_pair<ET, true><<<(unsigned) items, 256, 0, ctx->stream>>>(
-				    (const uint4 *) planes, Wp, a->n, t, items, S, Wk, a->norm, a->minLength, a->byteScale, (T *) D,
-				    (T *) N, rb, re, cd, cn, f0);
-			} else {
-				k_snp_tile_pair<ET, false><<<(unsigned) items, 256, 0, ctx->stream>>>(
-				    (const uint4 *) planes, Wp, a->n, t, items, 1, Wp, a->norm, a->minLength, a->byteScale, (T *) D,
-				    (T *) N, rb, re, cd, cn, f0);
-			}
-			CCG_CHECK(hipGetLastError());
-		}
-		if(S > 1) {
-			long long g = cdivll(f1 - f0, 256);
-			k_snp_pair_finish<ET><<<(unsigned) (g < 65536 ? g : 65536), 256, 0, ctx->stream>>>(
-			    cd, cn, f0, f1, a->norm, a->minLength, a->byteScale, (T *) D, (T *) N);
-			CCG_CHECK(hipGetLastError());
-			CCG_CHECK(hipStreamSynchronize(ctx->stream));
-			CCG_CHECK(hipFree(cd));
-		}
-		return CCG_OK;
-	}
-	// MFMA forms (k_snp_mfma3 / k_snp_mfma2 the default, k_snp_mfma with CCG_DIST_MFMA=1,
-	// the VALU tiles with 0): f32-exact while a slice holds < MFMA_KMAX words
-	if(dist_kernel_choice() == 2) return snp_launch_mfma2<ET>(ctx, a, planes, Wp, nFactor, D, rb, re, 0, 0);
-	const int use_mfma = dist_kernel_choice();
-	int Sm = S, Wkm = Wk;
-	if(use_mfma && Wkm > MFMA_KMAX) {
-		Wkm = (MFMA_KMAX / kc) * kc;
-		Sm = (int) cdivll(Wp, Wkm);
-	}
-	if(use_mfma) {
-		S = Sm;
-	}
-	const long long mi_begin = t_begin * S, mi_end = t_end * S;
-	unsigned *cnt = NULL;
-	if(S > 1) {
-		CCG_CHECK(hipMalloc(&cnt, (size_t) (f1 - f0) * sizeof(unsigned)));
-		CCG_CHECK(hipMemsetAsync(cnt, 0, (size_t) (f1 - f0) * sizeof(unsigned), ctx->stream));
-	}
-	for(long long t = use_mfma ? mi_begin : i_begin; t < (use_mfma ? mi_end : i_end); t += batch) {
-		const long long iend = use_mfma ? mi_end : i_end;
-		long long items = iend - t < batch ? iend - t : batch;
-		if(use_mfma) {
-			if(S > 1)
-				k_snp_mfma<ET, true><<<(unsigned) items, 256, 0, ctx->stream>>>((const uint2 *) planes, Wp, a->n, t, items,
-				                                                             S, Wkm, nFactor, a->byteScale, (T *) D, rb,
-				                                                             re, cnt, f0);
-			else
-				k_snp_mfma<ET, false><<<(unsigned) items, 256, 0, ctx->stream>>>((const uint2 *) planes, Wp, a->n, t,
-				                                                              items, 1, Wp, nFactor, a->byteScale,
-				                                                              (T *) D, rb, re, cnt, f0);
-		} else if(S > 1) {
-			k_snp_tile<ET, true><<<(unsigned) items, 256, 0, ctx->stream>>>((const uint2 *) planes, Wp, a->n, t, items, S,
-			                                                             Wk, nFactor, a->byteScale, (T *) D, rb, re,
-			                                                             cnt, f0);
-		} else {
-			k_snp_tile<ET, false><<<(unsigned) items, 256, 0, ctx->stream>>>((const uint2 *) planes, Wp, a->n, t, items,
-			                                                              1, Wp, nFactor, a->byteScale, (T *) D, rb,
-			                                                              re, cnt, f0);
-		}
-		CCG_CHECK(hipGetLastError());
-	}
-	if(S > 1) {
-		long long g = cdivll(f1 - f0, 256);
-		k_snp_finish<ET><<<(unsigned) (g < 65536 ? g : 65536), 256, 0, ctx->stream>>>(cnt, f0, f0, f1, nFactor,
-		                                                                                a->byteScale, (T *) D);
-		CCG_CHECK(hipGetLastError());
-		CCG_CHECK(hipStreamSynchronize(ctx->stream));
-		CCG_CHECK(hipFree(cnt));
-	}
-	return CCG_OK;
-}
-
-// the rank's owned rows of the band layout, in its own order: panels of TILE
-// owned rows, each against the column tiles below its last row
-template <int ET>
-static int snp_launch_band(ccg_ctx *ctx, const ccg_snp_args *a, const void *planes, int Wp, double nFactor, void *D,
-                           int rank, int world) {
+static int snp_launch_tile128(ccg_ctx *ctx, const ccg_snp_args *a, const void *planes, int Wp, double nFactor, void *D,
+                              void *N, long long rb, long long re, int rank, int world, bool mfma) {
 	typedef typename Elem<ET>::T T;
 	const long long n = a->n;
-	auto row_of = [&](long long L) {
-		const long long lb = L / SB;
-		return (lb * world + rank) * SB + (L - lb * SB);
-	};
-	long long nloc = 0;   // owned rows below n
-	const long long nb = (n + SB - 1) / SB;
-	if(rank < nb) {
-		const long long owned = (nb - 1 - rank) / world + 1, last = (owned - 1) * world + rank;
-		nloc = (owned - 1) * SB + (n - last * SB < SB ? n - last * SB : SB);
+	hipDeviceProp_t prop;
+	CCG_CHECK(hipGetDeviceProperties(&prop, ctx->device));
+	TileRange tr;
+	const int trc = tile_range(ctx, n, rb, re, rank, world, TILE, &tr);
+	if(trc != CCG_OK || (world > 0 && tr.npanels == 0)) return trc;
+	const long long f0 = tr.f0, f1 = tr.f1;
+	const bool pair = a->pair != 0;
+	const SplitPlan plan = plan_split(tr.t_end - tr.t_begin, 2LL * prop.multiProcessorCount, Wp, pair ? KCP : KC,
+	                                  mfma && !pair ? MFMA_KMAX : 0);
+	const int S = plan.S, Wk = plan.Wk;
+	if(pair && Wk >= MFMA_KMAX) mfma = false;
+	const long long batch = world > 0 ? 1 << 16 : 1 << 14;
+	T *Nn = world > 0 ? NULL : (T *) N;
+	unsigned *cnt = NULL;
+	int rc = CCG_OK;
+	if(S > 1 && (rc = alloc_counts(ctx, (size_t) (f1 - f0) * (pair ? 2 : 1), &cnt)) != CCG_OK) goto out;
+	for(long long t = tr.t_begin * S; t < tr.t_end * S; t += batch) {
+		const long long items = tr.t_end * S - t < batch ? tr.t_end * S - t : batch;
+		with_split_band(S > 1, world > 0, [&](auto SP, auto BD) {
+			constexpr bool sp = decltype(SP)::value, bd = decltype(BD)::value;
+			const uint2 *pl = (const uint2 *) planes;
+			const uint4 *pp = (const uint4 *) planes;
+			unsigned *cn = cnt ? cnt + (f1 - f0) : NULL;
+			if(pair && mfma)
+				k_snp_mfma_pair<ET, sp, bd><<<(unsigned) items, 256, 0, ctx->stream>>>(
+				    pp, Wp, (int) n, t, items, S, Wk, a->norm, a->minLength, a->byteScale, (T *) D, Nn, rb, re, cnt, cn, f0,
+				    tr.d_pfx, tr.npanels, rank, world);
+			else if(pair)
+				k_snp_tile_pair<ET, sp, bd><<<(unsigned) items, 256, 0, ctx->stream>>>(
+				    pp, Wp, (int) n, t, items, S, Wk, a->norm, a->minLength, a->byteScale, (T *) D, Nn, rb, re, cnt, cn, f0,
+				    tr.d_pfx, tr.npanels, rank, world);
+			else if(mfma)
+				k_snp_mfma<ET, sp, bd><<<(unsigned) items, 256, 0, ctx->stream>>>(
+				    pl, Wp, (int) n, t, items, S, Wk, nFactor, a->byteScale, (T *) D, rb, re, cnt, f0, tr.d_pfx, tr.npanels,
+				    rank, world);
+			else
+				k_snp_tile<ET, sp, bd><<<(unsigned) items, 256, 0, ctx->stream>>>(
+				    pl, Wp, (int) n, t, items, S, Wk, nFactor, a->byteScale, (T *) D, rb, re, cnt, f0, tr.d_pfx, tr.npanels,
+				    rank, world);
+		});
+		SNP_TRY(hipGetLastError());
 	}
+	if(S > 1) SNP_TRY(launch_finish<ET>(ctx, a, cnt, f0, f1, nFactor, (T *) D, Nn));
+	SNP_TRY(hipStreamSynchronize(ctx->stream));
+out:
+	return launch_exit(ctx, rc, cnt, tr.d_pfx);
+}
+#undef SNP_TRY
+
+// One matrix: the LT rows [rb, re) (world == 0) or one rank's rows of the band
+// layout (world > 0; rb = 0, re = n).  CCG_DIST_MFMA picks the kernels: 2 (the
+// default) the 256 x 256 MFMA tiles, 1 the 128 x 128 MFMA tiles, 0 the VALU
+// tiles.  Pair mode with -P runs k_snp_pair_proxi whatever it says.
+template <int ET>
+static int snp_launch(ccg_ctx *ctx, const ccg_snp_args *a, const void *planes, int Wp, double nFactor, void *D, void *N,
+                      long long rb, long long re, int rank, int world) {
+	typedef typename Elem<ET>::T T;
 	if(a->pair && a->proxi) {
-		// maskProxi pairs: an owned band's rows are contiguous in both the full
-		// LT and the rank's buffer with the same relative offsets, so each run of
-		// consecutive owned bands is k_snp_pair_proxi over its LT range with D
-		// shifted by off(first row) - tri(first row)
 		const int W32 = (a->len + 31) / 32;
+		// maskProxi pairs of the LT elements [f0, f1)
+		const auto run = [&](long long f0, long long f1, T *Dg, T *Ng) {
+			const long long g = cdivll(f1 - f0, 4);
+			if(f1 <= f0) return hipSuccess;
+			k_snp_pair_proxi<ET><<<(unsigned) (g < 16384 ? g : 16384), 256, 0, ctx->stream>>>(
+			    (const uint4 *) planes, Wp, W32, a->len, (int) a->proxi, f0, f1, a->norm, a->minLength, a->byteScale, Dg,
+			    Ng);
+			return hipGetLastError();
+		};
+		if(world == 0) {
+			CCG_CHECK(run(tri(rb), tri(re), (T *) D, (T *) N));
+			return CCG_OK;
+		}
+		// an owned band's rows are contiguous in both the full LT and the rank's
+		// buffer with the same relative offsets, so each run of consecutive owned
+		// bands is k_snp_pair_proxi over its LT range with D shifted by
+		// off(first row) - tri(first row)
+		const long long n = a->n, nb = cdivll(n, SB);
 		const Shard sh{rank, world};
 		for(long long g = rank; g < nb;) {
 			long long g2 = g;
 			while(world == 1 && g2 + 1 < nb) ++g2;   // world 1 owns every band
 			const long long r0 = g * SB, r1 = (g2 + 1) * SB < n ? (g2 + 1) * SB : n;
-			const long long f0 = tri(r0), f1 = tri(r1), gr = cdivll(f1 - f0, 4);
-			T *Dg = (T *) D + (sh.off(r0) - f0);
-			if(f1 > f0) {
-				k_snp_pair_proxi<ET><<<(unsigned) (gr < 16384 ? gr : 16384), 256, 0, ctx->stream>>>(
-				    (const uint4 *) planes, Wp, W32, a->len, (int) a->proxi, f0, f1, a->norm, a->minLength,
-				    a->byteScale, Dg, (T *) NULL);
-				CCG_CHECK(hipGetLastError());
-			}
+			CCG_CHECK(run(tri(r0), tri(r1), (T *) D + (sh.off(r0) - tri(r0)), (T *) NULL));
 			g = g2 + world;
 		}
 		CCG_CHECK(hipStreamSynchronize(ctx->stream));
 		return CCG_OK;
 	}
-	// tiles per panel (column tiles with a cell j < i), prefix-summed so that a
-	// launch spans many panels and fills the chip
-	const int npanels = (int) cdivll(nloc, TILE);
-	if(npanels == 0) return CCG_OK;
-	std::vector<long long> pfx(npanels + 1, 0);
-	for(long long I = 0; I < npanels; ++I) {
-		const long long Lmax = (I + 1) * TILE - 1 < nloc - 1 ? (I + 1) * TILE - 1 : nloc - 1;
-		pfx[I + 1] = pfx[I] + cdivll(row_of(Lmax), TILE);
-	}
-	long long *d_pfx = NULL;
-	CCG_CHECK(hipMalloc(&d_pfx, (size_t) (npanels + 1) * sizeof(long long)));
-	CCG_CHECK(hipMemcpyAsync(d_pfx, pfx.data(), (size_t) (npanels + 1) * sizeof(long long), hipMemcpyHostToDevice,
-	                         ctx->stream));
-	const long long total = pfx[npanels], batch = 1 << 16;
-	// the MFMA form unless disabled (CCG_DIST_MFMA=0); a row longer than the
-	// f32-exact slice is split over word slices
 	const char *mf = getenv("CCG_DIST_MFMA");
-	if(a->pair && dist_kernel_choice() == 2) {
-		CCG_CHECK(hipFree(d_pfx));
-		return snp_launch_mfma2<ET, true>(ctx, a, planes, Wp, nFactor, D, 0, n, rank, world);
-	}
-	if(a->pair) {
-		// fsacmpair per cell, the pair tiles in the band form; split-K over word
-		// slices (as snp_launch) when the rank's tiles do not fill the chip, the
-		// u32 counts indexed by local element and finished in place
-		hipDeviceProp_t prop;
-		CCG_CHECK(hipGetDeviceProperties(&prop, ctx->device));
-		const long long slots = 2LL * prop.multiProcessorCount;
-		const int chunks = Wp / KCP;
-		int S = 1;
-		if(total < 16 * slots) {
-			S = (int) cdivll(16 * slots, total);
-			if(S > chunks / 4) S = chunks / 4;
-			if(S < 1) S = 1;
-		}
-		const int Wk = (int) cdivll(chunks, S) * KCP;
-		S = (int) cdivll(Wp, Wk);
-		const bool pm = (mf ? atoi(mf) : 1) && Wk < MFMA_KMAX;
-		const long long elems = ccg_shard_elems(n, rank, world);
-		unsigned *cd = NULL, *cn = NULL;
-		if(S > 1) {
-			CCG_CHECK(hipMalloc(&cd, (size_t) elems * 2 * sizeof(unsigned)));
-			cn = cd + elems;
-			CCG_CHECK(hipMemsetAsync(cd, 0, (size_t) elems * 2 * sizeof(unsigned), ctx->stream));
-		}
-		for(long long t = 0; t < total * S; t += batch) {
-			const long long items = total * S - t < batch ? total * S - t : batch;
-			if(pm && S > 1)
-				k_snp_mfma_pair<ET, true, true><<<(unsigned) items, 256, 0, ctx->stream>>>(
-				    (const uint4 *) planes, Wp, (int) n, t, items, S, Wk, a->norm, a->minLength, a->byteScale, (T *) D,
-				    (T *) NULL, 0, n, cd, cn, 0, d_pfx, npanels, rank, world);
-			else if(pm)
-				k_snp_mfma_pair<ET, false, true><<<(unsigned) items, 256, 0, ctx->stream>>>(
-				    (const uint4 *) planes, Wp, (int) n, t, items, 1, Wp, a->norm, a->minLength, a->byteScale, (T *) D,
-				    (T *) NULL, 0, n, NULL, NULL, 0, d_pfx, npanels, rank, world);
-			else if(S > 1)
-				k_snp_tile_pair<ET, true, true><<<(unsigned) items, 256, 0, ctx->stream>>>(
-				    (const uint4 *) planes, Wp, (int) n, t, items, S, Wk, a->norm, a->minLength, a->byteScale, (T *) D,
-				    (T *) NULL, 0, n, cd, cn, 0, d_pfx, npanels, rank, world);
-			else
-				k_snp_tile_pair<ET, false, true><<<(unsigned) items, 256, 0, ctx->stream>>>(
-				    (const uint4 *) planes, Wp, (int) n, t, items, 1, Wp, a->norm, a->minLength, a->byteScale, (T *) D,
-				    (T *) NULL, 0, n, NULL, NULL, 0, d_pfx, npanels, rank, world);
-			CCG_CHECK(hipGetLastError());
-		}
-		if(S > 1) {
-			const long long g = cdivll(elems, 256);
-			k_snp_pair_finish<ET><<<(unsigned) (g < 65536 ? g : 65536), 256, 0, ctx->stream>>>(
-			    cd, cn, 0, elems, a->norm, a->minLength, a->byteScale, (T *) D, (T *) NULL);
-			CCG_CHECK(hipGetLastError());
-		}
-		CCG_CHECK(hipStreamSynchronize(ctx->stream));
-		if(cd) CCG_CHECK(hipFree(cd));
-		CCG_CHECK(hipFree(d_pfx));
-		return CCG_OK;
-	}
-	if(dist_kernel_choice() == 2) {
-		CCG_CHECK(hipFree(d_pfx));
-		return snp_launch_mfma2<ET>(ctx, a, planes, Wp, nFactor, D, 0, n, rank, world);
-	}
-	if(mf ? atoi(mf) : 1) {
-		// the MFMA form with snp_launch's split-K over word slices when the
-		// rank's tiles do not fill the chip, or when a row exceeds the f32-exact
-		// slice length; u32 counts by local element, k_snp_finish in place
-		hipDeviceProp_t prop;
-		CCG_CHECK(hipGetDeviceProperties(&prop, ctx->device));
-		const long long slots = 2LL * prop.multiProcessorCount;
-		const int chunks = Wp / KC;
-		int S = 1;
-		if(total < 16 * slots) {
-			S = (int) cdivll(16 * slots, total);
-			if(S > chunks / 4) S = chunks / 4;
-			if(S < 1) S = 1;
-		}
-		int Wk = (int) cdivll(chunks, S) * KC;
-		if(Wk > MFMA_KMAX) Wk = (MFMA_KMAX / KC) * KC;
-		S = (int) cdivll(Wp, Wk);
-		const long long elems = ccg_shard_elems(n, rank, world);
-		unsigned *cnt = NULL;
-		if(S > 1) {
-			CCG_CHECK(hipMalloc(&cnt, (size_t) elems * sizeof(unsigned)));
-			CCG_CHECK(hipMemsetAsync(cnt, 0, (size_t) elems * sizeof(unsigned), ctx->stream));
-		}
-		for(long long t = 0; t < total * S; t += batch) {
-			const long long items = total * S - t < batch ? total * S - t : batch;
-			if(S > 1)
-				k_snp_mfma_band<ET, true><<<(unsigned) items, 256, 0, ctx->stream>>>(
-				    (const uint2 *) planes, Wp, (int) n, d_pfx, npanels, t, items, nFactor, a->byteScale, (T *) D, rank,
-				    world, S, Wk, cnt);
-			else
-				k_snp_mfma_band<ET><<<(unsigned) items, 256, 0, ctx->stream>>>((const uint2 *) planes, Wp, (int) n,
-				                                                             d_pfx, npanels, t, items, nFactor,
-				                                                             a->byteScale, (T *) D, rank, world);
-			CCG_CHECK(hipGetLastError());
-		}
-		if(S > 1) {
-			const long long g = cdivll(elems, 256);
-			k_snp_finish<ET><<<(unsigned) (g < 65536 ? g : 65536), 256, 0, ctx->stream>>>(cnt, 0, 0, elems, nFactor,
-			                                                                                a->byteScale, (T *) D);
-			CCG_CHECK(hipGetLastError());
-		}
-		CCG_CHECK(hipStreamSynchronize(ctx->stream));
-		if(cnt) CCG_CHECK(hipFree(cnt));
-		CCG_CHECK(hipFree(d_pfx));
-		return CCG_OK;
-	}
-	for(long long t = 0; t < total; t += batch) {
-		const long long items = total - t < batch ? total - t : batch;
-		k_snp_tile_band<ET><<<(unsigned) items, 256, 0, ctx->stream>>>((const uint2 *) planes, Wp, (int) n, d_pfx,
-			                                                             npanels, t, items, nFactor, a->byteScale, (T *) D,
-			                                                             rank, world);
-		CCG_CHECK(hipGetLastError());
-	}
-	CCG_CHECK(hipStreamSynchronize(ctx->stream));
-	CCG_CHECK(hipFree(d_pfx));
-	return CCG_OK;
+	const int mode = mf ? atoi(mf) : 2;
+	if(mode != 2) return snp_launch_tile128<ET>(ctx, a, planes, Wp, nFactor, D, N, rb, re, rank, world, mode != 0);
+	if(a->pair) return snp_launch_mfma2<ET, true>(ctx, a, planes, Wp, nFactor, D, N, rb, re, rank, world);
+	return snp_launch_mfma2<ET, false>(ctx, a, planes, Wp, nFactor, D, N, rb, re, rank, world);
 }
 
 static int snp_run(ccg_ctx *ctx, const ccg_snp_args *a, void *D, void *N, int *inc_out, int rank, int world,
@@ -2651,19 +2196,12 @@ static int snp_run(ccg_ctx *ctx, const ccg_snp_args *a, void *D, void *N, int *i
 	int rc = CCG_OK;
 	ctx->dist_ms = 0;
 	CCG_CHECK(hipEventRecord(ctx->ev0, ctx->stream));
-	if(world > 0) {
+	if(re > rb) {   // a shard takes every row: rb = 0, re = n
 		switch(a->etype) {
-			case 8: rc = snp_launch_band<8>(ctx, a, planes, Wp, nFactor, D, rank, world); break;
-			case 4: rc = snp_launch_band<4>(ctx, a, planes, Wp, nFactor, D, rank, world); break;
-			case 2: rc = snp_launch_band<2>(ctx, a, planes, Wp, nFactor, D, rank, world); break;
-			default: rc = snp_launch_band<1>(ctx, a, planes, Wp, nFactor, D, rank, world); break;
-		}
-	} else if(re > rb) {
-		switch(a->etype) {
-			case 8: rc = snp_launch<8>(ctx, a, planes, Wp, nFactor, D, N, rb, re); break;
-			case 4: rc = snp_launch<4>(ctx, a, planes, Wp, nFactor, D, N, rb, re); break;
-			case 2: rc = snp_launch<2>(ctx, a, planes, Wp, nFactor, D, N, rb, re); break;
-			default: rc = snp_launch<1>(ctx, a, planes, Wp, nFactor, D, N, rb, re); break;
+			case 8: rc = snp_launch<8>(ctx, a, planes, Wp, nFactor, D, N, rb, re, rank, world); break;
+			case 4: rc = snp_launch<4>(ctx, a, planes, Wp, nFactor, D, N, rb, re, rank, world); break;
+			case 2: rc = snp_launch<2>(ctx, a, planes, Wp, nFactor, D, N, rb, re, rank, world); break;
+			default: rc = snp_launch<1>(ctx, a, planes, Wp, nFactor, D, N, rb, re, rank, world); break;
 		}
 	}
 	CCG_CHECK(hipEventRecord(ctx->ev1, ctx->stream));

@@ -337,6 +337,56 @@ def test_dist_shard_layout(dev, n, L, et, norm, world):
         dev.free(pi)
 
 
+# (n, L, etype, norm), worlds, CCG_DIST_MFMA modes.  SB = 8, so every shape
+# spans many bands.  (300, 4000): Wp = 128 words, several LDS chunks per slice,
+# and the plan splits K (band + SPLIT in both 128-tile kernels); three 128-row
+# panels, the last partial.  (517, 2049): a word tail, short etype, nFactor != 1.
+# (129, 1000): one row past a panel edge, byte etype.  (70, 6e6): a row longer
+# than the f32-exact slice, so the clamp forces SPLIT on the band MFMA kernel.
+_LEGACY_BAND = [((300, 4000, 8, 0), [1, 2, 3, 8], ["1", "0"]),
+                ((517, 2049, 2, 100), [1, 2, 3, 8], ["1", "0"]),
+                ((129, 1000, 1, 0), [1, 2, 3, 8], ["1", "0"]),
+                ((70, 6_000_000, 8, 0), [2], ["1"])]
+_legacy_band_ref = {}   # the latest shape's (seqs, inc, W, full): computed once per shape
+
+
+@pytest.mark.parametrize("n,L,et,norm,world,mfma", [(*shape, world, mode) for shape, worlds, modes in _LEGACY_BAND
+                                                    for world in worlds for mode in modes])
+def test_dist_shard_layout_legacy(dev, monkeypatch, n, L, et, norm, world, mfma):
+    """test_dist_shard_layout for the non-pair band shard of the 128-tile
+    kernels (CCG_DIST_MFMA=1: k_snp_mfma, 0: k_snp_tile, both with BAND): each
+    rank's buffer equals, element for element, the band extract of the full LT
+    from the default engine."""
+    import ccphylo_amd as cg
+    from ccphylo_amd import native as nt
+    key = (n, L, et, norm)
+    if key not in _legacy_band_ref:
+        monkeypatch.delenv("CCG_DIST_MFMA", raising=False)
+        seqs, inc, W = _rand_msa(n, L, n + L)
+        full, _, _ = dev.snp_ltd(seqs, inc, n, L, norm=norm, etype=et, byte_scale=2.0)
+        _legacy_band_ref.clear()
+        _legacy_band_ref[key] = (seqs, inc, W, full)
+    seqs, inc, W, full = _legacy_band_ref[key]
+    monkeypatch.setenv("CCG_DIST_MFMA", mfma)
+    dt = cg.ETYPES[et]
+    ps, pi = dev.malloc(seqs.nbytes), dev.malloc(inc.nbytes)
+    dev.h2d(ps, seqs)
+    dev.h2d(pi, inc)
+    try:
+        for rank in range(world):
+            m = nt.shard_elems(n, rank, world)
+            pd = dev.malloc(max(m, 1) * et)
+            dev.snp_ltd_shard_dev(ps, pi, n, L, W, pd, rank, world, norm=norm, etype=et, byte_scale=2.0)
+            got = np.empty(m, dtype=dt)
+            if m:
+                dev.d2h(got, pd)
+            dev.free(pd)
+            assert (got == nt.shard_extract(full, n, rank, world)).all()
+    finally:
+        dev.free(ps)
+        dev.free(pi)
+
+
 def test_dist_shard_to_tree_in_place(dev):
     """configs[4] in miniature on one GPU: dist writes the shard, the sharded
     DNJ consumes it in place; joins equal the single-GPU tree's."""
