@@ -32,6 +32,7 @@ struct ccg_ctx {
 	hipEvent_t ev0, ev1;
 	char name[256];
 	float dist_ms;   // the last dist call's pair kernels (HIP events on the engine stream)
+	int dist_slices, dist_slice_words;   // its split-K plan (plan_split; 0, 0: no tile kernel ran)
 	int flags;       // CCG_CTX_* (ccg_ctx_configure)
 	int masked;      // the stream was created with a CU mask (ccg_ctx_configure)
 	int ncu, cus;    // the device's CUs; the CUs the stream may use (0: all)

@@ -1749,22 +1749,32 @@ static int tile_range(ccg_ctx *ctx, long long n, long long rb, long long re, int
 // times over (so the tail round of blocks is small), each tile's Wp words are
 // cut into S slices of Wk words, a multiple of the kernel's kc-word chunk; a
 // slice keeps >= 4 chunks.  kmax > 0: and Wk <= kmax (the f32-exact slice of
-// the MFMA forms), however many tiles there are.
+// the MFMA forms), however many tiles there are.  CCG_DIST_SLICES=S (S >= 1, a
+// diagnostic knob) takes the place of the fill-the-chip choice: S slices, at
+// most one per chunk (no 4-chunk floor), then the same rounding and clamp, so
+// a test picks the chunks a slice gets whatever the device's CU count.  The
+// plan is kept in the context (ccg_last_dist_plan).
 struct SplitPlan {
 	int S, Wk;
 };
 
-static SplitPlan plan_split(long long tiles, long long slots, int Wp, int kc, int kmax) {
+static SplitPlan plan_split(ccg_ctx *ctx, long long tiles, long long slots, int Wp, int kc, int kmax) {
 	const int chunks = Wp / kc;
+	const char *fse = getenv("CCG_DIST_SLICES");
+	const int forced = fse ? atoi(fse) : 0;
 	int S = 1;
-	if(tiles < 16 * slots) {
+	if(forced >= 1) {
+		S = forced < chunks ? forced : chunks;
+	} else if(tiles < 16 * slots) {
 		S = (int) cdivll(16 * slots, tiles);
 		if(S > chunks / 4) S = chunks / 4;
 		if(S < 1) S = 1;
 	}
 	int Wk = (int) cdivll(chunks, S) * kc;
 	if(kmax && Wk > kmax) Wk = (kmax / kc) * kc;
-	return SplitPlan{(int) cdivll(Wp, Wk), Wk};
+	ctx->dist_slices = (int) cdivll(Wp, Wk);
+	ctx->dist_slice_words = Wk;
+	return SplitPlan{ctx->dist_slices, Wk};
 }
 
 // the kernels' SPLIT and BAND template arguments from two runtime values:
@@ -1836,7 +1846,7 @@ static int snp_launch_mfma2(ccg_ctx *ctx, const ccg_snp_args *a, const void *pla
 	const char *gle = getenv("CCG_DIST_GLDS");
 	const bool glds = !PAIR && !(gle && atoi(gle) == 0) && kc == KC3;
 	const int sorder = !PAIR && world == 0 && ore && atoi(ore) == 1 && (rb / TILE2) % 4 == 0;
-	const SplitPlan plan = plan_split(t_end - t_begin, prop.multiProcessorCount, Wp, kc, MFMA_KMAX);   // one block per CU
+	const SplitPlan plan = plan_split(ctx, t_end - t_begin, prop.multiProcessorCount, Wp, kc, MFMA_KMAX);   // one block per CU
 	const int S = plan.S, Wk = plan.Wk;
 	const long long batch = 1 << 16;
 	T *Nn = world > 0 ? NULL : (T *) N;
@@ -1918,7 +1928,7 @@ static int snp_launch_tile128(ccg_ctx *ctx, const ccg_snp_args *a, const void *p
 	if(trc != CCG_OK || (world > 0 && tr.npanels == 0)) return trc;
 	const long long f0 = tr.f0, f1 = tr.f1;
 	const bool pair = a->pair != 0;
-	const SplitPlan plan = plan_split(tr.t_end - tr.t_begin, 2LL * prop.multiProcessorCount, Wp, pair ? KCP : KC,
+	const SplitPlan plan = plan_split(ctx, tr.t_end - tr.t_begin, 2LL * prop.multiProcessorCount, Wp, pair ? KCP : KC,
 	                                  mfma && !pair ? MFMA_KMAX : 0);
 	const int S = plan.S, Wk = plan.Wk;
 	if(pair && Wk >= MFMA_KMAX) mfma = false;
@@ -2082,6 +2092,7 @@ static int snp_run(ccg_ctx *ctx, const ccg_snp_args *a, void *D, void *N, int *i
                    bool host_in) {
 	if(!a || a->n < 0 || a->len <= 0 || a->stride < (a->len + 31) / 32) return CCG_EINVAL;
 	if(a->etype != 8 && a->etype != 4 && a->etype != 2 && a->etype != 1) return CCG_EINVAL;
+	ctx->dist_slices = ctx->dist_slice_words = 0;   // until a launcher plans (n < 2 and -P's k_snp_pair_proxi: none)
 	if(a->n < 2) {
 		if(inc_out && !a->pair && host_in) {
 			int s = 0;
@@ -2218,6 +2229,13 @@ static int snp_run(ccg_ctx *ctx, const ccg_snp_args *a, void *D, void *N, int *i
 extern "C" int ccg_last_dist_ms(ccg_ctx *ctx, double *ms) {
 	if(!ctx || !ms) return CCG_EINVAL;
 	*ms = ctx->dist_ms;
+	return CCG_OK;
+}
+
+extern "C" int ccg_last_dist_plan(ccg_ctx *ctx, int *slices, int *slice_words) {
+	if(!ctx || !slices || !slice_words) return CCG_EINVAL;
+	*slices = ctx->dist_slices;
+	*slice_words = ctx->dist_slice_words;
 	return CCG_OK;
 }
 

@@ -118,7 +118,7 @@ ENGINE_SYMBOLS = [
     "ccg_shard_owner", "ccg_shard_row_offset", "ccg_shard_elems",
     "ccg_rccl_unique_id", "ccg_rccl_open", "ccg_rccl_close", "ccg_rccl_abort", "ccg_tree_shard", "ccg_tree_shard_dev",
     "ccg_kma_ltd", "ccg_kma_ltd_dev", "ccg_snp_ltd_shard_dev", "ccg_snp_ltd_shard", "ccg_selftest_row_sum",
-    "ccg_round_decimal_dev", "ccg_last_dist_ms", "ccg_tree_dev_state", "ccg_tree_shard_bytes", "ccg_ctx_configure",
+    "ccg_round_decimal_dev", "ccg_last_dist_ms", "ccg_last_dist_plan", "ccg_tree_dev_state", "ccg_tree_shard_bytes", "ccg_ctx_configure",
     "ccg_shutdown",
 ]
 # every symbol of include/ccphylo_host.h
@@ -472,6 +472,13 @@ class Device:
         ms = C.c_double(0)
         self._check(self.lib.ccg_last_dist_ms(self.h, C.byref(ms)), "ccg_last_dist_ms")
         return ms.value
+
+    def last_dist_plan(self):
+        """(slices, words per slice) of the last dist call's tile-kernel launch
+        (ccg_last_dist_plan); (0, 0) when it launched none (n < 2, pair mode with -P)."""
+        s, wk = C.c_int(0), C.c_int(0)
+        self._check(self.lib.ccg_last_dist_plan(self.h, C.byref(s), C.byref(wk)), "ccg_last_dist_plan")
+        return s.value, wk.value
 
     def selftest_row_sum(self, c):
         """The engine's exact-mode row sum of c (ccg_selftest_row_sum): returns

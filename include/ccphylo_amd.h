@@ -117,6 +117,13 @@ int ccg_snp_ltd_dev(ccg_ctx *ctx, const ccg_snp_args *a, void *D_dev, void *N_de
  * events on the engine stream; benchmarks use it for the roofline. */
 int ccg_last_dist_ms(ccg_ctx *ctx, double *ms);
 
+/* The split-K plan of the last dist call's pair-kernel launch on this
+ * context: every tile's words were cut into *slices slices of *slice_words
+ * words (the last one may be shorter).  0, 0 when the call launched no tile
+ * kernel (n < 2, or pair mode with -P).  Tests read it to assert the path
+ * they meant to take (with the CCG_DIST_SLICES knob). */
+int ccg_last_dist_plan(ccg_ctx *ctx, int *slices, int *slice_words);
+
 /* ------------------------------------------------------------------ */
 /* dist on KMA count matrices (matcmp.c:448 cmpMats per pair)          */
 /* ------------------------------------------------------------------ */

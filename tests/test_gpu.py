@@ -194,7 +194,10 @@ def test_dist_mfma_equals_valu(dev, monkeypatch, n, L, et, rows, pair):
     tetrahedron +-1 vectors in MX-fp4, dist = (3 L - dot) / 4, in pair mode
     masked with n from a fourth component) give the VALU tile kernels'
     matrices (and N) bit for bit: odd sizes, row ranges, split-K slices, every element type (the
-    default path, MFMA, is checked against the oracle by the tests above)."""
+    default path, MFMA, is checked against the oracle by the tests above).  The slices here are whatever
+    plan_split makes of the device's CU count: the 6 Mbp case has one 256 x 256 tile, cut into thousands of
+    short slices, and does not reach the f32-exact slice limit.  test_gpu_dist_slices.py forces the slice
+    count, sweeps the chunks per slice and runs slices at that limit."""
     import torch
     rng = np.random.default_rng(n + L)
     W = L // 32 + 1

@@ -94,3 +94,95 @@ def clade_packed(n, L, clades, seed=3, every=10, flips=8):
     if L % 32:
         incs[W32 - 1] &= np.uint32((0xFFFFFFFF << (32 - L % 32)) & 0xFFFFFFFF)
     return seqs, incs
+
+
+def _pack_codes(codes, W):
+    """2-bit codes of positions 0..len-1 into W u64 words, position p at bits
+    63 - 2p .. 62 - 2p of word p // 32 (qseqs.c:60); positions past len zero."""
+    pad = np.zeros(W * 32, dtype=np.uint64)
+    pad[:len(codes)] = codes
+    sh = np.uint64(62) - np.uint64(2) * np.arange(32, dtype=np.uint64)
+    return np.bitwise_or.reduce(pad.reshape(W, 32) << sh, axis=1)
+
+
+def staircase_packed(L, q, s, seed=5, holes=0.02):
+    """A packed alignment whose every distance is known in closed form
+    (staircase_truth), numpy only.  One random base sequence of L codes; taxon
+    t is the base with (code + s[t]) % 4 on the positions < q[t] (0 <= q[t] <=
+    L, s[t] in 1..3): a staircase of prefixes, so taxa with the same (q, s)
+    are identical and two taxa with q = L and different shifts differ
+    everywhere.  Built from the four packed shifts of the base by word copies
+    (and one mixed word per taxon), never an n x L code array.  The global
+    include mask drops each position with p = holes; its tail past L is
+    cleared as in clade_packed.  Returns (seqs n x W u64, W = L // 32 + 1;
+    incs W u32, include bit of position p = bit 31 - p % 32 of word p // 32;
+    the included count)."""
+    q = np.asarray(q, dtype=np.int64)
+    s = np.asarray(s, dtype=np.int64)
+    assert q.shape == s.shape and q.ndim == 1
+    assert ((q >= 0) & (q <= L)).all() and ((s >= 1) & (s <= 3)).all()
+    n, W = len(q), L // 32 + 1
+    rng = np.random.default_rng(seed)
+    base = rng.integers(0, 4, L, dtype=np.uint64)
+    forms = [_pack_codes((base + np.uint64(k)) % np.uint64(4), W) for k in range(4)]
+    seqs = np.empty((n, W), dtype=np.uint64)
+    for t in range(n):
+        wq, r = int(q[t]) // 32, int(q[t]) % 32
+        f = forms[int(s[t])]
+        seqs[t, :wq] = f[:wq]
+        seqs[t, wq:] = forms[0][wq:]
+        if r:   # the word the step falls in: its first r positions shifted
+            hm = np.uint64(((1 << (2 * r)) - 1) << (64 - 2 * r))
+            seqs[t, wq] = (f[wq] & hm) | (forms[0][wq] & ~hm)
+    bits = np.zeros(W * 32, dtype=np.uint8)
+    bits[:L] = rng.random(L) >= holes
+    incs = np.packbits(bits).view(">u4").astype(np.uint32)
+    return seqs, incs, int(bits.sum())
+
+
+def staircase_prefix(incs, L):
+    """C[x] = included positions < x of a packed include mask, x = 0..L (int64)."""
+    incs = np.ascontiguousarray(incs, dtype=np.uint32)
+    bits = np.unpackbits(incs.astype(">u4").view(np.uint8))[:L]
+    C = np.zeros(L + 1, dtype=np.int64)
+    np.cumsum(bits, dtype=np.int64, out=C[1:])
+    return C
+
+
+def staircase_truth(incs, L, q, s):
+    """The packed LT (cell (i, j), j < i, at i (i - 1) / 2 + j; int64) of the
+    non-pair SNP distances of staircase_packed(L, q, s) under the global mask
+    incs, from the mask alone: with C the prefix count of included positions,
+    dist(a, b) = [s_a != s_b] C(min q) + C(max q) - C(min q)
+    (below both steps the codes differ iff the shifts do; between the steps
+    one taxon is shifted and the other is not)."""
+    q = np.asarray(q, dtype=np.int64)
+    s = np.asarray(s, dtype=np.int64)
+    C = staircase_prefix(incs, L)
+    i, j = np.tril_indices(len(q), -1)
+    lo, hi = C[np.minimum(q[i], q[j])], C[np.maximum(q[i], q[j])]
+    return (s[i] != s[j]) * lo + hi - lo
+
+
+def staircase_pair_masks(incs, L, n, seed=6, empty=None):
+    """Per-taxon masks for pair mode (n x W u32): the global holes of incs
+    and-ed with one excluded interval per taxon (up to L / 8 positions long,
+    anywhere); taxon `empty` (default n // 2) is excluded entirely, so every
+    pair with it has no shared position and minLength yields -1."""
+    incs = np.ascontiguousarray(incs, dtype=np.uint32)
+    W = len(incs)
+    rng = np.random.default_rng(seed)
+    out = np.tile(incs, (n, 1))
+    full = np.uint64(0xFFFFFFFF)
+    for t in range(n):
+        ln = int(rng.integers(1, max(L // 8, 1) + 1))
+        a = int(rng.integers(0, L - ln + 1))
+        b = a + ln                                   # positions [a, b) excluded
+        wa, wb = a // 32, (b - 1) // 32
+        keep = np.full(wb - wa + 1, 0, dtype=np.uint64)
+        keep[0] |= (full << np.uint64(32 - a % 32)) & full if a % 32 else np.uint64(0)        # positions before a
+        keep[-1] |= full >> np.uint64(b - wb * 32) if b - wb * 32 < 32 else np.uint64(0)      # positions from b on
+        out[t, wa:wb + 1] &= keep.astype(np.uint32)
+    out[n // 2 if empty is None else empty] = 0
+    assert out.shape == (n, W)
+    return out
