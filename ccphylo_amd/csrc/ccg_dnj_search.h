@@ -9,182 +9,21 @@
 #pragma once
 #include <stdlib.h>
 #include "ccg_tree_common.h"
+#include "ccg_dnj_form.h"
 
 struct DenseRows {
 	__host__ __device__ __forceinline__ bool owns(long long) const { return true; }
 	__host__ __device__ __forceinline__ long long row(long long r) const { return tri(r); }
 };
 
-#define DNJ_B 128        // capacity of S, the candidate rows rescanned speculatively
-#define DNJ_BANDS 64     // S: the top rows with Q < m0, then the min-Q row of each
-                         // of this many bands below them (DnjGrid::top/bands)
-#define DNJ_BANDS_MAX 128  // CCG_S_BANDS up to this (two bands per lane of k_dnj_plan's wave 0)
-#define SEG 2048         // cells per rescan unit (TB threads x 8)
 #define SEG_S 1024       // cells per rescan unit of S's rows (pruning's S phase: shorter chains, more waves)
 #define SEL_RPL 8        // rows per lane per step of the S scan (<= 32)
 #define SEL_STEPS 8      // steps of the S scan at most (then the listing takes over)
-#define TBF 1024         // threads of k_dnj_plan (one block)
-#define FIND_RPT 16      // rows per thread per step of k_dnj_plan's listing (one step up to n = 15361)
 #define FIND_CHUNKS 2048  // 64-row chunks of k_dnj_plan's S-rank table (n <= 131072; else binary searches)
 #define REPLAY_CAP 2048  // rest entries staged in LDS
 #define JOIN_UPRE 2048   // rest-unit partials k_dnj_join prefetches into LDS
 #define FOLD_BLOCKS 256  // grid of k_dnj_fold (one wave per entry, grid-stride)
-#define PLAN_MAXB 256    // blocks of k_dnj_plan (one listing step of LT * FR rows each)
 #define SRDY_REP 64      // copies of the scan's S-table ready tag (pollers spread over lines)
-#define UHIST 64         // bins of k_dnj_plan's per-block histogram of entries by unit count (umax < UHIST)
-
-// Grid of k_dnj_scan: min(ceil(n / scan_div), scan_max).  CCG_SCAN_DIV and
-// CCG_SCAN_MAX override it (tests shrink the grid so that several grid
-// waves of units run at small n).
-struct DnjGrid {
-	// prefold_n: every n folds each entry's units once (k_dnj_fold + k_dnj_join_pf); round 4, measured: the
-	// headline's tree 6.61 -> 6.36 s (profiled), configs[1] 24.7k -> 25.0k joins/s, 4k Euclidean unchanged
-	int scan_div = 4, scan_max = 2048, seg_mul = 0, prefold_n = 0;
-	// below 16384 taxa the wave scan replaces the block scan while the joins list many rows: tree_run_t
-	// sets small_wave from the rows listed per join over its last 1024-join window (> adapt_rows;
-	// CCG_SCAN_ADAPT, 0: never; headline tree 6.23 -> 6.16 s at 1000, 6.11 at 500).  Clade SNP data (the headline) lists thousands of rows per join there,
-	// Euclidean matrices a few hundred (configs[1]: 246), where the block scan is 2-3 % faster
-	int small_wave = 0, adapt_rows = 500;
-	int sphase_b = 512;   // CCG_SPHASE_BLOCKS
-	// scan_prune 2: k_dnj_plan's helper blocks rescan S while the plan lists (CCG_PLAN_HELP; 0: S in
-	// k_dnj_sphase after the plan): headline tree 5.96 -> 5.71 (128) / 5.67 s (256), profiled
-	int plan_help = 256;
-	int scan_cmp = 1, cmp_blocks = 1024;   // the compacted wave scan (CCG_SCAN_CMP=0: off) and its grid
-	// scan_prune 2 pays while the joins list many cells: tree_run_t keeps it on (prune_on) while the last
-	// 1024-join window listed more than prune_cells cells per join (CCG_PRUNE_CELLS; 0: always)
-	long long prune_cells = 20000000;
-	int prune_on = 1;
-	// plan_qdelay: the listing waves hold their Q loads back by qdelay x 32 x 64 cycles so that wave 0's fold
-	// loads go first (round 6, profiles/r06_config1_sweep.txt: 0 -> 2 gives configs[1] 23.5k -> 23.9k joins/s,
-	// the headline tree 12.79k -> 12.90k; 4 and above lose at 10k)
-	int s_top = 0, s_bands = -1, s_split_n = 16384, plan_qdelay = 2, scan_wave = -1, plan_multi = 1;
-	int plan_regsel = 0, plan_fr = FIND_RPT;   // measured at 10k: S from registers 13.2 -> 15.4 us (Q arrives late), FR 1-8 within noise
-	// tests only (CCG_TEST_WITHHOLD): bit 0, k_dnj_plan's block 0 never publishes its entry count (the
-	// listing blocks' look-back must time out into an error); bit 1, it never tags the S header (the
-	// helper blocks' wait must); either shortens the bounded spins so that the error comes quickly
-	int test_withhold = 0;
-	int join_pf = 1;   // with k_dnj_fold: k_dnj_join_pf (0: k_dnj_join; 2: its block-0 replay path always)
-	// measured at the headline (configs[2], 50k, profiled tree; round 4): scan + fold per join 68.3 us with
-	// k_dnj_fold, 72.4 with FoldTail, 84.2 with FoldTail + pruning (cells 2.12x -> 1.27x the reference's:
-	// the S phase and the wait for its table lengthen every wave's chain more than the pruned loads save)
-	int scan_fold = 0; // the fold at the scan's last arrivals (FoldTail) instead of k_dnj_fold (CCG_SCAN_FOLD=1)
-	// band mode: the S rows' exact fresh minima bound the other entries, and an entry whose stale Q is not
-	// below the bound at its row is one minQpair skips (dnj.c:78): 2 (default) k_dnj_sphase rescans S,
-	// builds the table and keeps only the surviving entries for the compacted wave scan; 1: the S phase
-	// inside the scan (with FoldTail, CCG_SCAN_FOLD=1); 0: off.  Headline tree (profiled, round 4):
-	// 6.29 s off, 5.86-5.89 s with 2 while the joins list > 15-30M cells, 6.05 s with 2 throughout
-	int scan_prune = 2;
-	// the block lower bounds (TreeBufs::lbm, lb_unit): kept by the join and the requeue from the first join
-	// of a matrix larger than lb_min_n on (CCG_SCAN_LB=0: off; CCG_LB_MIN_N), used by the compacted wave scan
-	int lb = 1, lb_min_n = 16384;
-	// with the bounds, the row-group scan modes (20-23: float / u16 / u8 rows) may rescan bounded row groups
-	// (CCG_LB_GROUPS=1: k_dnj_scan_gc<LB>, lb_unit_g: one column-sum load per lane for the group's rows
-	// needing a block) instead of one bounded row per wave.  Measured (round 6, configs[3] on round 4's
-	// cdist matrix, first 40k joins, the same cells): scan 40.9 s against 17.2 s for one row per wave --
-	// the bounded scan is latency-bound, and the group form has a quarter of the units at 131 VGPRs
-	// (3 waves/SIMD) against 68 (7): off by default
-	int lb_groups = 0;
-	int scan_vblk = 1;  // with pruning: also the bound from every row above (the requeue's per-block
-	                    // minima of V_k = max(q at the partner cell, Q_k)) (CCG_SCAN_VBLK=0: off)
-	void load() {
-		if(const char *e = getenv("CCG_JOIN_PF")) join_pf = atoi(e);
-		if(const char *e = getenv("CCG_SCAN_FOLD")) scan_fold = atoi(e);
-		if(const char *e = getenv("CCG_SCAN_PRUNE")) scan_prune = atoi(e);
-		if(const char *e = getenv("CCG_SCAN_VBLK")) scan_vblk = atoi(e);
-		if(const char *e = getenv("CCG_S_TOP")) s_top = atoi(e) > 0 ? atoi(e) : 0;
-		if(const char *e = getenv("CCG_S_BANDS")) s_bands = atoi(e) >= 0 ? atoi(e) : -1;
-		if(const char *e = getenv("CCG_S_SPLIT_N")) s_split_n = atoi(e);
-		if(const char *e = getenv("CCG_SCAN_DIV")) scan_div = atoi(e) > 0 ? atoi(e) : 4;
-		if(const char *e = getenv("CCG_SCAN_MAX")) scan_max = atoi(e) > 0 ? atoi(e) : 2048;
-		if(const char *e = getenv("CCG_SEG_MUL")) seg_mul = atoi(e) > 0 ? atoi(e) : 0;
-		if(const char *e = getenv("CCG_PREFOLD_N")) prefold_n = atoi(e) >= 0 ? atoi(e) : 0;
-		if(const char *e = getenv("CCG_SCAN_ADAPT")) adapt_rows = atoi(e) > 0 ? atoi(e) : 0;
-		if(const char *e = getenv("CCG_SPHASE_BLOCKS")) sphase_b = atoi(e) > 0 ? atoi(e) : 512;
-		if(const char *e = getenv("CCG_PLAN_HELP")) plan_help = atoi(e) >= 0 && atoi(e) < 512 ? atoi(e) : 256;
-		if(const char *e = getenv("CCG_SCAN_CMP")) scan_cmp = atoi(e);
-		if(const char *e = getenv("CCG_PRUNE_CELLS")) prune_cells = atoll(e) > 0 ? atoll(e) : 0;
-		prune_on = 1;
-		if(const char *e = getenv("CCG_SCAN_CMPB")) cmp_blocks = atoi(e) > 0 ? atoi(e) : 1024;
-		if(const char *e = getenv("CCG_PLAN_QDELAY")) plan_qdelay = atoi(e) >= 0 ? atoi(e) : 2;
-		if(const char *e = getenv("CCG_SCAN_WAVE")) scan_wave = atoi(e);
-		if(const char *e = getenv("CCG_PLAN_MULTI")) plan_multi = atoi(e);
-		if(const char *e = getenv("CCG_PLAN_REGSEL")) plan_regsel = atoi(e);
-		if(const char *e = getenv("CCG_PLAN_FR")) plan_fr = atoi(e) < 1 ? 1 : atoi(e) > FIND_RPT ? FIND_RPT : atoi(e);
-		if(const char *e = getenv("CCG_TEST_WITHHOLD")) test_withhold = atoi(e) & 3;
-		if(const char *e = getenv("CCG_SCAN_LB")) lb = atoi(e);
-		if(const char *e = getenv("CCG_LB_MIN_N")) lb_min_n = atoi(e);
-		if(const char *e = getenv("CCG_LB_GROUPS")) lb_groups = atoi(e);
-	}
-	// k_dnj_plan's last argument: the Q-load delay (low 14 bits), bits 14-15 the
-	// test knob test_withhold, bit 16 turns
-	// the register S selection off (on with CCG_PLAN_REGSEL=1)
-	// and bits 17-20 the rows per thread per listing step less one (CCG_PLAN_FR)
-	int plan_flags(bool prune = false, int helpers = 0) const {
-		return (plan_qdelay & 0x3fff) | (test_withhold & 3) << 14 | (plan_regsel ? 0 : 1 << 16) | ((plan_fr - 1) & 15) << 17 | (prune ? 1 << 21 : 0) |
-		       (helpers & 511) << 22;
-	}
-	// k_dnj_plan's grid: one listing step of (TBF - 64) FIND_RPT rows per block
-	// (CCG_PLAN_MULTI=0: one block walks every step, the round-2 form)
-	unsigned plan_blocks(int n) const {
-		if(!plan_multi) return 1;
-		const int step = (TBF - 64) * plan_fr;
-		const int g = (n - 1 + step - 1) / step;
-		return (unsigned) (g < 1 ? 1 : g > PLAN_MAXB ? PLAN_MAXB : g);
-	}
-	// rescans one unit per wave past 16384 taxa, where the units are long:
-	// 16-byte row loads (k_dnj_scan_v, mode 4; the GEN form k_dnj_scan_w,
-	// mode 1); one unit per block below (k_dnj_scan, mode 0).  Measured per
-	// join at 50k (headline data): 88.4 (block) -> 72.0 (wave) -> 66.7 us
-	// (wave, 16-byte loads) -> 65.2 us (+ nontemporal row loads and 16-byte
-	// sD loads where aligned, mode 9; 8433 -> 8920 joins/s); 10k: 9.4 (block)
-	// against 9.8 us (wave).  Float rows take the row-group form (mode 20,
-	// k_dnj_scan_g, 4 rows per wave sharing the sD loads): configs[3]'s first
-	// 30k joins rescan in 34.0 s against 47.0 s with mode 4 on the same box
-	// (mode 4 41.7-47.0 s over boxes; 9: 46.0, 11: 46.8, 13: 47.0, 15: 47.5);
-	// double rows gain nothing from it at 50k (joins/s: G4/UC8 8472, G4/UC4
-	// 8453, G2/UC8 8656 against 8901 for mode 9; modes 20, 22, 23).
-	// In the sharded engine (no row groups) modes >= 4 run k_dnj_scan_v.
-	// CCG_SCAN_WAVE=0/1/4..19/20/21 forces a form.
-	// past 16384 taxa: double rows (the headline) stream with the 16-byte
-	// nontemporal wave scan (9); narrower rows (float -p, u16 -s, u8 -b) in row
-	// groups (20), where the 8-byte sD load per cell outweighs the row bytes
-	// and one sD load serves 4 rows
-	int scan_mode(int n, int et = 8) const {
-		return scan_wave >= 0 ? scan_wave : n > 16384 || small_wave ? (et == 8 ? 9 : 20) : 0;
-	}
-	// cells per rescan unit: SEG up to 8 units per row, then growing with n
-	// (at most 8 SEG) so that a unit's fixed cost stays small beside its bytes
-	int seg(int n) const {
-		int m = seg_mul ? seg_mul : n / (8 * SEG);
-		m = m < 1 ? 1 : m > 8 ? 8 : m;
-		return m * SEG;
-	}
-	// rows with many units: fold each row's unit partials once (k_dnj_fold)
-	// instead of in every block of k_dnj_join
-	bool prefold(int n) const { return n > prefold_n; }
-	// S: `top` rows from the top, then up to `bands` band-minimum rows.  Small
-	// matrices are latency-bound: 128 top rows, no bands; beyond s_split_n the
-	// bands cut the rescanned cells several-fold (tools/sim_stages.c)
-	int top(int n) const {
-		// (round 4: 8 top rows in band mode measured the same as 16 at the headline; band mode with pruning
-		// below 16384 taxa -- CCG_S_TOP=8 CCG_S_BANDS=64 -- took its tree 5.64 -> 5.43-5.51 s profiled, engine
-		// cells 1.31 -> 1.16x, but costs configs[1]'s Euclidean trees, and switching band mode per window
-		// needs the requeue and the next plan to agree; not done)
-		const int t = s_top ? s_top : n > s_split_n ? 16 : DNJ_B;
-		return t < 1 ? 1 : t > DNJ_B ? DNJ_B : t;
-	}
-	int bands(int n) const {
-		int b = s_bands >= 0 ? s_bands : n > s_split_n ? DNJ_BANDS : 0;
-		b = b > DNJ_BANDS_MAX ? DNJ_BANDS_MAX : b;
-		return top(n) + b > DNJ_B ? DNJ_B - top(n) : b;
-	}
-	// k_dnj_sphase's grid (one wave per S unit, grid-stride)
-	unsigned sphase_blocks() const { return sphase_b; }
-	unsigned scan(int n) const {
-		const long long g = (n + scan_div - 1) / scan_div;
-		return (unsigned) (g < scan_max ? g : scan_max);
-	}
-};
 
 // (trace stamps TS / TSW / TS_ENTRY / TS_EXIT / TS_SAMP: ccg_tree_common.h)
 
@@ -1337,7 +1176,6 @@ __global__ __launch_bounds__(TBF) void k_dnj_plan(const typename Elem<ET>::T *__
 // anywhere (the plan lists rows only).  Tail: work every block does first
 // (begin) and the store of each unit's partial (unit, thread 0), for the
 // sharded engine's records.
-__host__ __device__ __forceinline__ int dnj_umax(int n, int seg) { return n > 2 ? (n - 2) / seg + 1 : 1; }
 
 struct NoTail {
 	__device__ __forceinline__ void begin(const TreeBufs &, int) const {}
@@ -1676,12 +1514,12 @@ __global__ __launch_bounds__(TB) void k_dnj_scan_w(const typename Elem<ET>::T *_
 // so a float row streams at 1 KB per wave load instead of 256 B; the unit's
 // unaligned head and its tail (fewer than VEC cells each) are scalar.  sD is
 // gathered per cell.  UV vector loads in flight per lane (about 16 cells).
-// MODE (measurement variants, CCG_SCAN_WAVE = 4 + MODE): bit 0 streams the
-// row with nontemporal loads (read once; sD keeps the caches), bit 1
-// software-pipelines the unit: the next UV loads are issued before the
-// current ones are compared (half UV, two register sets), bit 2 loads sD
-// 16 bytes at a time where the unit's aligned start is even (sD + ca 16-byte
-// aligned; uniform per unit), bit 3 doubles the loads in flight per lane.
+// STREAM (CCG_SCAN_WAVE=9, the default for double rows): the row streams with
+// nontemporal loads (read once; sD keeps the caches) and sD loads 16 bytes
+// at a time where the unit's aligned start is even (sD + ca 16-byte aligned;
+// uniform per unit).  (Either alone, a software-pipelined unit with two
+// register sets and twice the loads in flight per lane were measured and
+// lost: DnjGrid::scan_mode.)
 // CMP (single engine, NoTail): the real units enumerated densely from the
 // plan's histogram of entries by unit count, slot-major (slot k: the E_k
 // entries with more than k units, a prefix of the descending list), and dealt
@@ -1864,14 +1702,12 @@ __device__ __forceinline__ long long lb_unit_g(const typename Elem<ET>::T *const
 	return span - loaded;
 }
 
-template <int ET, class Rows, class Tail = NoTail, int MODE = 0, int PRUNE = 0, bool CMP = false, bool LB = false>
+template <int ET, class Rows, class Tail = NoTail, bool STREAM = false, int PRUNE = 0, bool CMP = false, bool LB = false>
 __global__ __launch_bounds__(TB) void k_dnj_scan_v(const typename Elem<ET>::T *__restrict__ D, double bs, TreeBufs b,
                                                    int n, Rows rows, int seg, Tail tail = Tail()) {
 	typedef typename Elem<ET>::T T;
 	static_assert(!(LB && PRUNE == 1), "the block bounds serve the compacted scan (its S units fold elsewhere)");
-	constexpr bool NTL = MODE & 1, PIPE = (MODE & 2) != 0, SDV = (MODE & 4) != 0;
-	constexpr int VEC = 16 / (int) sizeof(T), UV0 = (VEC >= 16 ? 1 : 16 / VEC) * (MODE & 8 ? 2 : 1);
-	constexpr int UV = PIPE && UV0 > 1 ? UV0 / 2 : UV0;
+	constexpr int VEC = 16 / (int) sizeof(T), UV = VEC >= 16 ? 1 : 16 / VEC;
 	__shared__ int erow[REPLAY_CAP];
 	TreeCtl *ctl = b.ctl;
 	const int tid = threadIdx.x, lane = tid & 63;
@@ -1945,66 +1781,54 @@ __global__ __launch_bounds__(TB) void k_dnj_scan_v(const typename Elem<ET>::T *_
 		};
 		if(lane < ca - c0) cell(c0 + lane);   // the unaligned head
 		if(lane < c1 - ce) cell(ce + lane);   // the tail
-		uint4 w[2][UV];
-		double sk[2][UV][VEC];
-		const bool sda = SDV && (ca & 1) == 0;   // uniform
-		auto load = [&](int buf, int v0) {
+		uint4 w[UV];
+		double sk[UV][VEC];
+		const bool sda = STREAM && (ca & 1) == 0;   // uniform
+		auto load = [&](int v0) {
 #pragma unroll
 			for(int m = 0; m < UV; ++m) {
 				int k = v0 + 64 * m + lane;
 				k = k < nv ? k : nv - 1;
 				const uint4 *src = (const uint4 *) (row + ca + VEC * k);
-				if(NTL) {
+				if(STREAM) {
 					typedef unsigned u4v __attribute__((ext_vector_type(4)));
 					const u4v x = __builtin_nontemporal_load((const u4v *) src);
-					w[buf][m] = make_uint4(x.x, x.y, x.z, x.w);
+					w[m] = make_uint4(x.x, x.y, x.z, x.w);
 				} else {
-					w[buf][m] = *src;
+					w[m] = *src;
 				}
 				if(sda) {
 #pragma unroll
 					for(int t = 0; t < VEC; t += 2) {
 						const double2 x = *(const double2 *) (b.sD + ca + VEC * k + t);
-						sk[buf][m][t] = x.x;
-						sk[buf][m][t + 1] = x.y;
+						sk[m][t] = x.x;
+						sk[m][t + 1] = x.y;
 					}
 				} else {
 #pragma unroll
-					for(int t = 0; t < VEC; ++t) sk[buf][m][t] = b.sD[ca + VEC * k + t];
+					for(int t = 0; t < VEC; ++t) sk[m][t] = b.sD[ca + VEC * k + t];
 				}
 			}
 		};
-		auto compare = [&](int buf, int v0) {
+		auto compare = [&](int v0) {
 #pragma unroll
 			for(int m = 0; m < UV; ++m) {
 				const int k = v0 + 64 * m + lane;
-				const T *ev = (const T *) &w[buf][m];
+				const T *ev = (const T *) &w[m];
 #pragma unroll
 				for(int t = 0; t < VEC; ++t) {
 					const int c = ca + VEC * k + t;
 					const double d = Elem<ET>::get(ev[t], bs);
-					const double x = qcrit(n, n, d, sDr, sk[buf][m][t]);
+					const double x = qcrit(n, n, d, sDr, sk[m][t]);
 					const bool take = k < nv && 0 <= d && qarg_better(x, c, q, idx);
 					q = take ? x : q;
 					idx = take ? c : idx;
 				}
 			}
 		};
-		if(PIPE) {
-			if(nv > 0) load(0, 0);
-			int v0 = 0;
-			for(; v0 + 64 * UV < nv; v0 += 128 * UV) {
-				load(1, v0 + 64 * UV);
-				compare(0, v0);
-				if(v0 + 128 * UV < nv) load(0, v0 + 128 * UV);
-				compare(1, v0 + 64 * UV);
-			}
-			if(v0 < nv) compare(0, v0);
-		} else {
-			for(int v0 = 0; v0 < nv; v0 += 64 * UV) {
-				load(0, v0);
-				compare(0, v0);
-			}
+		for(int v0 = 0; v0 < nv; v0 += 64 * UV) {
+			load(v0);
+			compare(v0);
 		}
 		qarg_wave_reduce(q, idx);
 		if(PRUNE == 1 && sent) fold_arrive(b, n, b.uq, b.uj, u, sua, sub, q, idx, e, Tn, true);
@@ -2268,8 +2092,8 @@ __global__ __launch_bounds__(TB) void k_dnj_sphase(const typename Elem<ET>::T *_
 }
 
 // Row groups (the default rescan past 16384 taxa for every element type but
-// double, scan_mode 20; 21-23 are other (G, UC) forms for measurement,
-// CCG_SCAN_WAVE): one wave rescans
+// double, scan_mode 20; 21 is the (G, UC) = (8, 4) form, kept for measurement;
+// (4, 4) and (2, 8) were measured and lost, DnjGrid::scan_mode): one wave rescans
 // the same seg-cell column range of G consecutive entries, so each sD load
 // serves G rows (sD bytes per cell / G) and the wave holds G row streams in
 // flight; rows are read one cell per lane (4- or 8-byte loads, coalesced per
@@ -2451,7 +2275,7 @@ __global__ __launch_bounds__(TB) void k_dnj_scan_g(const typename Elem<ET>::T *_
 		atomicAdd((unsigned long long *) &ctl->cells_pruned, (unsigned long long) pruned);
 }
 
-// Row groups over a dense enumeration (scan_mode 20-23 with the compacted
+// Row groups over a dense enumeration (scan_mode 20, 21 with the compacted
 // form, the single engine's default for float / u16 / u8 rows past 16384
 // taxa): the entries to rescan -- every listed entry, or with pruning
 // (PRUNE2, k_dnj_sphase ran) only the survivors k_dnj_sphase appended to

@@ -1786,30 +1786,63 @@ static int tree_alloc_ctx(ccg_ctx *c, TreeWork *w, int n) {
 }
 
 // DNJ: k_dnj_plan of the join at matrix size n (first: the run's first join,
-// whose candidate k_dnj_prep or a resumed state left in ctl)
-// the scan rescans S first and prunes the other entries under S's exact
-// fresh minima: band mode, the wave scans with the fold at their last
-// arrivals, no missing entries
-// (scan_prune 1: the S phase inside the scan, with FoldTail; 2: S rescanned by
-// k_dnj_sphase, its own launch, then the wave scan with k_dnj_fold)
-static int dnj_prune(int n, int et, bool gen) {
-	const int sm = g_grid.scan_mode(n, et);
-	if(gen || !g_grid.bands(n) || !g_grid.prefold(n)) return 0;
-	if(g_grid.scan_prune == 1 && g_grid.scan_fold && ((sm >= 4 && sm < 20) || (sm >= 20 && sm <= 23))) return 1;
-	// prune 2 with the row groups: the compacted group scan (k_dnj_scan_gc) enumerates the survivors
-	const bool gcmp = sm >= 20 && sm <= 23 && g_grid.scan_cmp && dnj_umax(n, g_grid.seg(n)) < UHIST;
-	if(g_grid.scan_prune == 2 && g_grid.prune_on && !g_grid.scan_fold && ((sm >= 4 && sm < 20) || gcmp)) return 2;
-	return 0;
+// whose candidate k_dnj_prep or a resumed state left in ctl).  With pruning
+// (ScanForm::prune) the plan also leaves S's header for the bound table, and
+// its helper blocks rescan S while it lists.
+template <int ET, bool GEN>
+static void enqueue_plan(hipStream_t st, typename Elem<ET>::T *D, double bs, const TreeBufs &b, int n, int first,
+                         const ScanForm &f) {
+	const int seg = g_grid.seg(n);
+	const unsigned gp = g_grid.plan_blocks(n);
+	if(g_grid.bands(n)) k_dnj_plan<ET, GEN, DenseRows, true><<<gp + f.helpers, TBF, 0, st>>>(D, bs, b, n, first, DenseRows(), seg, g_grid.top(n), g_grid.bands(n), g_grid.plan_flags(f.prune != 0, f.helpers));
+	else k_dnj_plan<ET, GEN, DenseRows, false><<<gp, TBF, 0, st>>>(D, bs, b, n, first, DenseRows(), seg, g_grid.top(n), 0, g_grid.plan_flags());
+}
+
+// The scan of the form f (dnj_scan_form): each kernel instantiation is named
+// once, here.  k_dnj_scan_v's forms per streaming setting, then the row
+// groups' per (G, UC), then the kernel.
+template <int ET, bool STREAM>
+static void launch_scan_v(const ScanForm &f, hipStream_t st, typename Elem<ET>::T *D, double bs, const TreeBufs &b, int n, int seg) {
+	const DenseRows dr;
+	if(f.cmp && f.prune == 2) k_dnj_scan_v<ET, DenseRows, NoTail, STREAM, 2, true><<<f.grid, TB, 0, st>>>(D, bs, b, n, dr, seg);
+	else if(f.cmp) k_dnj_scan_v<ET, DenseRows, NoTail, STREAM, 0, true><<<f.grid, TB, 0, st>>>(D, bs, b, n, dr, seg);
+	else if(f.prune == 2) k_dnj_scan_v<ET, DenseRows, NoTail, STREAM, 2><<<f.grid, TB, 0, st>>>(D, bs, b, n, dr, seg);
+	else if(f.prune == 1) k_dnj_scan_v<ET, DenseRows, FoldTail, STREAM, 1><<<f.grid, TB, 0, st>>>(D, bs, b, n, dr, seg);
+	else if(f.tfold) k_dnj_scan_v<ET, DenseRows, FoldTail, STREAM><<<f.grid, TB, 0, st>>>(D, bs, b, n, dr, seg);
+	else k_dnj_scan_v<ET, DenseRows, NoTail, STREAM><<<f.grid, TB, 0, st>>>(D, bs, b, n, dr, seg);
+}
+
+template <int ET, int G, int UC>
+static void launch_scan_g(const ScanForm &f, hipStream_t st, typename Elem<ET>::T *D, double bs, const TreeBufs &b, int n, int seg) {
+	if(f.cmp && f.prune == 2) k_dnj_scan_gc<ET, G, UC, true><<<f.grid, TB, 0, st>>>(D, bs, b, n, seg);
+	else if(f.cmp) k_dnj_scan_gc<ET, G, UC, false><<<f.grid, TB, 0, st>>>(D, bs, b, n, seg);
+	else if(f.prune) k_dnj_scan_g<ET, G, UC, true, true><<<f.grid, TB, 0, st>>>(D, bs, b, n, seg);
+	else if(f.tfold) k_dnj_scan_g<ET, G, UC, true><<<f.grid, TB, 0, st>>>(D, bs, b, n, seg);
+	else k_dnj_scan_g<ET, G, UC><<<f.grid, TB, 0, st>>>(D, bs, b, n, seg);
 }
 
 template <int ET, bool GEN>
-static void enqueue_plan(hipStream_t st, typename Elem<ET>::T *D, double bs, const TreeBufs &b, int n, int first) {
-	const int seg = g_grid.seg(n);
-	const unsigned gp = g_grid.plan_blocks(n);
-	const int prune = dnj_prune(n, ET, GEN);
-	const int nh = prune == 2 && g_grid.plan_help ? g_grid.plan_help : 0;   // S's rescans by helper blocks
-	if(g_grid.bands(n)) k_dnj_plan<ET, GEN, DenseRows, true><<<gp + nh, TBF, 0, st>>>(D, bs, b, n, first, DenseRows(), seg, g_grid.top(n), g_grid.bands(n), g_grid.plan_flags(prune != 0, nh));
-	else k_dnj_plan<ET, GEN, DenseRows, false><<<gp, TBF, 0, st>>>(D, bs, b, n, first, DenseRows(), seg, g_grid.top(n), 0, g_grid.plan_flags());
+static void enqueue_scan(const ScanForm &f, hipStream_t st, typename Elem<ET>::T *D, double bs, const TreeBufs &b, int n, int seg) {
+	const DenseRows dr;
+	switch(f.kernel) {
+		case SCAN_BLOCK: k_dnj_scan<ET, GEN><<<f.grid, TB, 0, st>>>(D, bs, b, n, dr, seg); break;
+		case SCAN_WAVE:
+			if(f.tfold) k_dnj_scan_w<ET, GEN, DenseRows, FoldTail><<<f.grid, TB, 0, st>>>(D, bs, b, n, dr, seg);
+			else k_dnj_scan_w<ET, GEN><<<f.grid, TB, 0, st>>>(D, bs, b, n, dr, seg);
+			break;
+		case SCAN_WAVE16:   // (bounded: the compacted form, plain loads)
+			if(f.lb && f.prune == 2) k_dnj_scan_v<ET, DenseRows, NoTail, false, 2, true, true><<<f.grid, TB, 0, st>>>(D, bs, b, n, dr, seg);
+			else if(f.lb) k_dnj_scan_v<ET, DenseRows, NoTail, false, 0, true, true><<<f.grid, TB, 0, st>>>(D, bs, b, n, dr, seg);
+			else if(f.stream) launch_scan_v<ET, true>(f, st, D, bs, b, n, seg);
+			else launch_scan_v<ET, false>(f, st, D, bs, b, n, seg);
+			break;
+		case SCAN_GROUP:
+		case SCAN_GROUP_CMP:   // (bounded: 4 rows per wave share each column-sum load)
+			if(f.lb) k_dnj_scan_gc<ET, 4, 8, false, true><<<f.grid, TB, 0, st>>>(D, bs, b, n, seg);
+			else if(f.G == 8) launch_scan_g<ET, 8, 4>(f, st, D, bs, b, n, seg);
+			else launch_scan_g<ET, 4, 8>(f, st, D, bs, b, n, seg);
+			break;
+	}
 }
 
 // One join's kernels for a matrix of n taxa; returns the launch count.
@@ -1820,112 +1853,19 @@ static int enqueue_iteration(hipStream_t st, typename Elem<ET>::T *D, double bs,
 	const int general = GEN;
 	const int xs = 0;   // exact row sums: split over the join kernel and its consumer (xs_join_row, xs_walk_blocks)
 	if(method == CCG_TREE_DNJ) {
-		const unsigned gc = g_grid.scan(n);
 		const int seg = g_grid.seg(n), prefold = g_grid.prefold(n);
+		const ScanForm f = dnj_scan_form(g_grid, n, ET, GEN, b.lbm != NULL);
 		// one-phase search: k_dnj_plan lists S and the rows below it under the
-		// partner-cell bound, k_dnj_scan rescans them all
-		enqueue_plan<ET, GEN>(st, D, bs, b, n, first);
+		// partner-cell bound, the scan rescans them all (with pruning: S first,
+		// by k_dnj_sphase or the plan's helpers, the rest under S's bound table)
+		enqueue_plan<ET, GEN>(st, D, bs, b, n, first, f);
 		kt.mark(CCG_K_FIND);
-		const int sm = g_grid.scan_mode(n, ET);
-		// the wave-per-unit scans fold the entries at their last arrivals
-		// (FoldTail) instead of a k_dnj_fold pass
-		const bool tfold = prefold && g_grid.scan_fold && sm >= 1;
-		const int prune = dnj_prune(n, ET, GEN);
-		if(prune == 2 && g_grid.plan_help) k_dnj_sphase<ET, false><<<g_grid.sphase_blocks(), TB, 0, st>>>(D, bs, b, n, seg);
-		else if(prune == 2) k_dnj_sphase<ET><<<g_grid.sphase_blocks(), TB, 0, st>>>(D, bs, b, n, seg);
-		if(b.lbm && !GEN && sm >= 20 && sm <= 23 && g_grid.lb_groups && g_grid.scan_cmp && !tfold && prune == 0 &&
-		   dnj_umax(n, seg) < UHIST) {
-			// bounded row groups (float / u16 / u8 rows): 4 rows per wave share each column-sum load
-			const unsigned gcc = gc < (unsigned) g_grid.cmp_blocks ? gc : (unsigned) g_grid.cmp_blocks;
-			k_dnj_scan_gc<ET, 4, 8, false, true><<<gcc, TB, 0, st>>>(D, bs, b, n, seg);
-		} else if(b.lbm && !GEN && sm >= 4 && g_grid.scan_cmp && !tfold && prune != 1 && dnj_umax(n, seg) < UHIST) {
-			// the compacted wave scan under the block lower bounds (every element type)
-			const unsigned gcc = gc < (unsigned) g_grid.cmp_blocks ? gc : (unsigned) g_grid.cmp_blocks;
-			if(prune == 2) k_dnj_scan_v<ET, DenseRows, NoTail, 0, 2, true, true><<<gcc, TB, 0, st>>>(D, bs, b, n, DenseRows(), seg);
-			else k_dnj_scan_v<ET, DenseRows, NoTail, 0, 0, true, true><<<gcc, TB, 0, st>>>(D, bs, b, n, DenseRows(), seg);
-		} else if(sm >= 20 && sm <= 23 && !GEN && g_grid.scan_cmp && !tfold && prune != 1 && dnj_umax(n, seg) < UHIST) {
-			// row groups over the dense (group, unit) enumeration; with pruning, the survivors only
-			const unsigned gcc = gc < (unsigned) g_grid.cmp_blocks ? gc : (unsigned) g_grid.cmp_blocks;
-			if(prune == 2) {
-				if(sm == 20) k_dnj_scan_gc<ET, 4, 8, true><<<gcc, TB, 0, st>>>(D, bs, b, n, seg);
-				else if(sm == 21) k_dnj_scan_gc<ET, 8, 4, true><<<gcc, TB, 0, st>>>(D, bs, b, n, seg);
-				else if(sm == 22) k_dnj_scan_gc<ET, 4, 4, true><<<gcc, TB, 0, st>>>(D, bs, b, n, seg);
-				else k_dnj_scan_gc<ET, 2, 8, true><<<gcc, TB, 0, st>>>(D, bs, b, n, seg);
-			} else {
-				if(sm == 20) k_dnj_scan_gc<ET, 4, 8, false><<<gcc, TB, 0, st>>>(D, bs, b, n, seg);
-				else if(sm == 21) k_dnj_scan_gc<ET, 8, 4, false><<<gcc, TB, 0, st>>>(D, bs, b, n, seg);
-				else if(sm == 22) k_dnj_scan_gc<ET, 4, 4, false><<<gcc, TB, 0, st>>>(D, bs, b, n, seg);
-				else k_dnj_scan_gc<ET, 2, 8, false><<<gcc, TB, 0, st>>>(D, bs, b, n, seg);
-			}
-		} else if(sm >= 20 && sm <= 23 && !GEN) {
-			if(prune) {
-				if(sm == 20) k_dnj_scan_g<ET, 4, 8, true, true><<<gc, TB, 0, st>>>(D, bs, b, n, seg);
-				else if(sm == 21) k_dnj_scan_g<ET, 8, 4, true, true><<<gc, TB, 0, st>>>(D, bs, b, n, seg);
-				else if(sm == 22) k_dnj_scan_g<ET, 4, 4, true, true><<<gc, TB, 0, st>>>(D, bs, b, n, seg);
-				else k_dnj_scan_g<ET, 2, 8, true, true><<<gc, TB, 0, st>>>(D, bs, b, n, seg);
-			} else if(tfold) {
-				if(sm == 20) k_dnj_scan_g<ET, 4, 8, true><<<gc, TB, 0, st>>>(D, bs, b, n, seg);
-				else if(sm == 21) k_dnj_scan_g<ET, 8, 4, true><<<gc, TB, 0, st>>>(D, bs, b, n, seg);
-				else if(sm == 22) k_dnj_scan_g<ET, 4, 4, true><<<gc, TB, 0, st>>>(D, bs, b, n, seg);
-				else k_dnj_scan_g<ET, 2, 8, true><<<gc, TB, 0, st>>>(D, bs, b, n, seg);
-			} else {
-				if(sm == 20) k_dnj_scan_g<ET, 4, 8><<<gc, TB, 0, st>>>(D, bs, b, n, seg);
-				else if(sm == 21) k_dnj_scan_g<ET, 8, 4><<<gc, TB, 0, st>>>(D, bs, b, n, seg);
-				else if(sm == 22) k_dnj_scan_g<ET, 4, 4><<<gc, TB, 0, st>>>(D, bs, b, n, seg);
-				else k_dnj_scan_g<ET, 2, 8><<<gc, TB, 0, st>>>(D, bs, b, n, seg);
-			}
-		} else if(sm >= 4 && !GEN) {
-			// the compacted form (the plan's unit histogram; umax within its bins)
-			const bool cmp = g_grid.scan_cmp && prune != 1 && !tfold && dnj_umax(n, seg) < UHIST;
-			const unsigned gcc = gc < (unsigned) g_grid.cmp_blocks ? gc : (unsigned) g_grid.cmp_blocks;
-			if(cmp && prune == 2) {
-				switch(sm) {
-#define SV_(M) case 4 + M: k_dnj_scan_v<ET, DenseRows, NoTail, M, 2, true><<<gcc, TB, 0, st>>>(D, bs, b, n, DenseRows(), seg); break;
-					SV_(1) SV_(5) SV_(7) SV_(13)
-#undef SV_
-					default: k_dnj_scan_v<ET, DenseRows, NoTail, 0, 2, true><<<gcc, TB, 0, st>>>(D, bs, b, n, DenseRows(), seg);
-				}
-			} else if(cmp) {
-				switch(sm) {
-#define SV_(M) case 4 + M: k_dnj_scan_v<ET, DenseRows, NoTail, M, 0, true><<<gcc, TB, 0, st>>>(D, bs, b, n, DenseRows(), seg); break;
-					SV_(1) SV_(5) SV_(7) SV_(13)
-#undef SV_
-					default: k_dnj_scan_v<ET, DenseRows, NoTail, 0, 0, true><<<gcc, TB, 0, st>>>(D, bs, b, n, DenseRows(), seg);
-				}
-			} else if(prune == 2) {
-				switch(sm) {
-#define SV_(M) case 4 + M: k_dnj_scan_v<ET, DenseRows, NoTail, M, 2><<<gc, TB, 0, st>>>(D, bs, b, n, DenseRows(), seg); break;
-					SV_(1) SV_(5)
-#undef SV_
-					default: k_dnj_scan_v<ET, DenseRows, NoTail, 0, 2><<<gc, TB, 0, st>>>(D, bs, b, n, DenseRows(), seg);
-				}
-			} else if(prune) {
-				switch(sm) {
-#define SV_(M) case 4 + M: k_dnj_scan_v<ET, DenseRows, FoldTail, M, true><<<gc, TB, 0, st>>>(D, bs, b, n, DenseRows(), seg); break;
-					SV_(1) SV_(5)
-#undef SV_
-					default: k_dnj_scan_v<ET, DenseRows, FoldTail, 0, true><<<gc, TB, 0, st>>>(D, bs, b, n, DenseRows(), seg);
-				}
-			} else if(tfold) {
-				switch(sm) {
-#define SV_(M) case 4 + M: k_dnj_scan_v<ET, DenseRows, FoldTail, M><<<gc, TB, 0, st>>>(D, bs, b, n, DenseRows(), seg); break;
-					SV_(1) SV_(5)
-#undef SV_
-					default: k_dnj_scan_v<ET, DenseRows, FoldTail><<<gc, TB, 0, st>>>(D, bs, b, n, DenseRows(), seg);
-				}
-			} else {
-				switch(sm) {
-#define SV_(M) case 4 + M: k_dnj_scan_v<ET, DenseRows, NoTail, M><<<gc, TB, 0, st>>>(D, bs, b, n, DenseRows(), seg); break;
-					SV_(1) SV_(2) SV_(3) SV_(4) SV_(5) SV_(6) SV_(7) SV_(13) SV_(15)
-#undef SV_
-					default: k_dnj_scan_v<ET, DenseRows><<<gc, TB, 0, st>>>(D, bs, b, n, DenseRows(), seg);
-				}
-			}
-		} else if(sm >= 1) {
-			if(tfold) k_dnj_scan_w<ET, GEN, DenseRows, FoldTail><<<gc, TB, 0, st>>>(D, bs, b, n, DenseRows(), seg);
-			else k_dnj_scan_w<ET, GEN><<<gc, TB, 0, st>>>(D, bs, b, n, DenseRows(), seg);
-		} else k_dnj_scan<ET, GEN><<<gc, TB, 0, st>>>(D, bs, b, n, DenseRows(), seg);
-		if(prefold && !tfold) k_dnj_fold<><<<FOLD_BLOCKS, TB, 0, st>>>(b, n, seg, prune == 2);
+		if(f.sphase == SPHASE_COMPACT) k_dnj_sphase<ET, false><<<g_grid.sphase_blocks(), TB, 0, st>>>(D, bs, b, n, seg);
+		else if(f.sphase == SPHASE_SCAN) k_dnj_sphase<ET><<<g_grid.sphase_blocks(), TB, 0, st>>>(D, bs, b, n, seg);
+		enqueue_scan<ET, GEN>(f, st, D, bs, b, n, seg);
+		// (the wave-per-unit scans may fold the entries at their last arrivals,
+		// FoldTail, instead of this pass)
+		if(f.fold) k_dnj_fold<><<<FOLD_BLOCKS, TB, 0, st>>>(b, n, seg, f.sfold);
 		kt.mark(CCG_K_REST);
 		if(prefold && g_grid.join_pf) k_dnj_join_pf<ET, GEN><<<gn, TB, 0, st>>>(D, bs, b, n, general, g_grid.join_pf == 2);
 		else k_dnj_join<ET, GEN><<<gn, TB, 0, st>>>(D, bs, b, n, general, prefold, seg);
@@ -1935,12 +1875,13 @@ static int enqueue_iteration(hipStream_t st, typename Elem<ET>::T *D, double bs,
 			k_exact_sum<><<<1, XS_NT, 0, st>>>(b, n, (int) gn);
 			kt.mark(CCG_K_XSUM);
 		}
-		if(g_grid.bands(n - 1) && g_grid.scan_vblk && dnj_prune(n - 1, ET, GEN))
+		// the requeue leaves the V block minima for the next join's pruning
+		if(g_grid.bands(n - 1) && g_grid.scan_vblk && dnj_scan_form(g_grid, n - 1, ET, GEN, b.lbm != NULL).prune)
 			k_dnj_requeue<ET, true, true><<<gn, TB, 0, st>>>(D, bs, b, n, general, exact);
 		else if(g_grid.bands(n - 1)) k_dnj_requeue<ET, true><<<gn, TB, 0, st>>>(D, bs, b, n, general, exact);
 		else k_dnj_requeue<ET, false><<<gn, TB, 0, st>>>(D, bs, b, n, general, exact);
 		kt.mark(CCG_K_REQUEUE);
-		return (GEN ? 5 : 4) + (prefold && !tfold) + (prune == 2) + xs;
+		return (GEN ? 4 : 3) + f.launches + xs;   // plan, join (+ update), requeue; the scan leg
 	}
 	if(method == CCG_TREE_HNJ) {
 		k_hnj_argmin<><<<gn, TB, 0, st>>>(b, n);
@@ -2261,8 +2202,8 @@ static int tree_run_t(ccg_ctx *ctx, const ccg_tree_args *a, void *Dd, ccg_join *
 				// into Q/P of rows j and i (and moves row n's sD/N to i) and
 				// picks the candidate (minPos, dnj.c:1026-1032); nothing after
 				// it in this run reads what else it lists
-				if(general) enqueue_plan<ET, true>(st, D, bs, b, n, 0);
-				else enqueue_plan<ET, false>(st, D, bs, b, n, 0);
+				if(general) enqueue_plan<ET, true>(st, D, bs, b, n, 0, dnj_scan_form(g_grid, n, ET, true, b.lbm != NULL));
+				else enqueue_plan<ET, false>(st, D, bs, b, n, 0, dnj_scan_form(g_grid, n, ET, false, b.lbm != NULL));
 				CCG_CHECK(hipGetLastError());
 			}
 			TreeCtl h2;   // h keeps the run's counters (the extra plan adds its S cells)

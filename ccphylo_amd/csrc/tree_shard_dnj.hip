@@ -901,7 +901,6 @@ static int tree_shard_dnj_run_t(ccg_ctx *ctx, const ccg_tree_args *a, const ccg_
 		while(n > stop_n) {
 			const unsigned gn = cdiv(n, TB), gp = cdiv(n, PICK_T) < PICK_MAXB ? cdiv(n, PICK_T) : PICK_MAXB;
 			T *Xmr = X + 2 * (size_t) n;   // row n-1, gathered with lines i and j
-			const unsigned gc = grid.scan(n);
 			const int seg = grid.seg(n);
 			// one-phase search (k_dnj_plan): each rank lists the S rows and the
 			// rows below S it owns, under the bound of its own S rows' partner
@@ -913,12 +912,21 @@ static int tree_shard_dnj_run_t(ccg_ctx *ctx, const ccg_tree_args *a, const ccg_
 			if(grid.bands(n)) k_dnj_plan<ET, false, Shard, true><<<gpl, TBF, 0, st>>>(D, bs, b, n, n == n0, sh, seg, grid.top(n), grid.bands(n), grid.plan_flags());
 			else k_dnj_plan<ET, false, Shard, false><<<gpl, TBF, 0, st>>>(D, bs, b, n, n == n0, sh, seg, grid.top(n), 0, grid.plan_flags());
 			kt.mark(CCG_K_FIND);
-			if(b.lbm && grid.scan_mode(n, ET) == 9) k_dnj_scan_v<ET, Shard, RecTail<ET>, 5, 0, false, true><<<gc, TB, 0, st>>>(D, bs, b, n, sh, seg, RecTail<ET>{D, sh, Sl, pcnt});
-			else if(b.lbm && grid.scan_mode(n, ET) >= 4) k_dnj_scan_v<ET, Shard, RecTail<ET>, 0, 0, false, true><<<gc, TB, 0, st>>>(D, bs, b, n, sh, seg, RecTail<ET>{D, sh, Sl, pcnt});
-			else if(grid.scan_mode(n, ET) == 9) k_dnj_scan_v<ET, Shard, RecTail<ET>, 5><<<gc, TB, 0, st>>>(D, bs, b, n, sh, seg, RecTail<ET>{D, sh, Sl, pcnt});
-			else if(grid.scan_mode(n, ET) >= 4) k_dnj_scan_v<ET, Shard, RecTail<ET>><<<gc, TB, 0, st>>>(D, bs, b, n, sh, seg, RecTail<ET>{D, sh, Sl, pcnt});
-			else if(grid.scan_mode(n, ET)) k_dnj_scan_w<ET, false, Shard, RecTail<ET>><<<gc, TB, 0, st>>>(D, bs, b, n, sh, seg, RecTail<ET>{D, sh, Sl, pcnt});
-			else k_dnj_scan<ET, false><<<gc, TB, 0, st>>>(D, bs, b, n, sh, seg, RecTail<ET>{D, sh, Sl, pcnt});
+			{
+				// the scan of this join's form; each kernel instantiation is named once
+				const ScanForm f = dnj_scan_form_shard(grid, n, ET, b.lbm != NULL);
+				const RecTail<ET> rt{D, sh, Sl, pcnt};
+				switch(f.kernel) {
+					case SCAN_WAVE16:
+						if(f.lb && f.stream) k_dnj_scan_v<ET, Shard, RecTail<ET>, true, 0, false, true><<<f.grid, TB, 0, st>>>(D, bs, b, n, sh, seg, rt);
+						else if(f.lb) k_dnj_scan_v<ET, Shard, RecTail<ET>, false, 0, false, true><<<f.grid, TB, 0, st>>>(D, bs, b, n, sh, seg, rt);
+						else if(f.stream) k_dnj_scan_v<ET, Shard, RecTail<ET>, true><<<f.grid, TB, 0, st>>>(D, bs, b, n, sh, seg, rt);
+						else k_dnj_scan_v<ET, Shard, RecTail<ET>><<<f.grid, TB, 0, st>>>(D, bs, b, n, sh, seg, rt);
+						break;
+					case SCAN_WAVE: k_dnj_scan_w<ET, false, Shard, RecTail<ET>><<<f.grid, TB, 0, st>>>(D, bs, b, n, sh, seg, rt); break;
+					default: k_dnj_scan<ET, false><<<f.grid, TB, 0, st>>>(D, bs, b, n, sh, seg, rt);
+				}
+			}
 			kt.mark(CCG_K_REST);
 			SD_TRY(cr.allgather(Sl, G, rec_slot(n, sh.world).bytes));
 			k_shd_pick<ET><<<gp, PICK_T, 0, st>>>(D, b, n, sh, G, X, pacc, pflag, n0, dbg);

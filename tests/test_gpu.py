@@ -560,6 +560,31 @@ def test_dnj_scan_row_groups(dev, monkeypatch, mode, kind, n, et):
     assert len(got) == len(ref) and (got == ref).all()
 
 
+@pytest.mark.parametrize("kind,n,et,retired,base", [("clade", 2500, 8, "13", "4"), ("euc", 2000, 4, "23", "20")])
+def test_dnj_scan_retired_modes(dev, monkeypatch, kind, n, et, retired, base):
+    """A retired CCG_SCAN_WAVE value runs the form of its base value
+    (dnj_scan_form: 5-8 and 10-19 as 4, 22 and 23 as 20): the same joins and
+    lengths, the same rescanned cells and reference-rule counters, and both
+    equal to the serial reference."""
+    from oracle import pyoracle
+    from ccphylo_amd import native
+    K = native.NKSTAT
+    monkeypatch.setenv("CCG_PREFOLD_N", "0")
+    monkeypatch.setenv("CCG_SEG_MUL", "1")
+    D = _euclid(n, n + 9).astype(np.float32) if kind == "euc" else _clade_ltd(n, n + 8)
+    ref, rfn, rfd, rst = pyoracle.tree(D, n, etype=et, method=1, stats=True)
+    runs = {}
+    for mode in (retired, base):
+        monkeypatch.setenv("CCG_SCAN_WAVE", mode)
+        got, fn, fd, st = dev.tree(D, n, etype=et, method=1, exact=True, profile=True)
+        assert (fn, fd) == (rfn, rfd), mode
+        assert len(got) == len(ref) and (got == ref).all(), mode
+        assert (st[10 + 2 * K], st[11 + 2 * K]) == (int(rst[0]), int(rst[1])), mode
+        runs[mode] = (got, st[1], st[10 + 2 * K], st[11 + 2 * K])
+    assert (runs[retired][0] == runs[base][0]).all()
+    assert runs[retired][1:] == runs[base][1:]
+
+
 def _state_equal(g, r, n):
     """An engine checkpoint (ccg_dnj_state + its device LT) against the
     oracle's DnjState after the same joins: every vector bit for bit."""
@@ -666,8 +691,8 @@ def test_dist_compacted_words(dev, monkeypatch, n, L, et, excl, norm):
                                             ("clade", 2200, 8, "1"), ("miss", 1400, 8, "1"), ("snp", 1800, 2, "20")])
 def test_dnj_scan_tail_fold(dev, monkeypatch, kind, n, et, mode):
     """The fold of each entry's unit partials and the 64-entry chunk
-    summaries at the scan's last arrivals (FoldTail, the default past 16384
-    taxa) instead of a k_dnj_fold pass, at small n through CCG_PREFOLD_N=0
+    summaries at the scan's last arrivals (FoldTail, CCG_SCAN_FOLD=1; the
+    default is 0) instead of a k_dnj_fold pass, at small n through CCG_PREFOLD_N=0
     and small rescan units (many units per row, many arrivals per entry):
     wave scans with 16-byte loads (9, 4), row groups (20), the GEN wave scan
     with missing entries (1); joins bit-identical to the serial reference and
