@@ -202,6 +202,25 @@ def kma_adversarial(path, L, seed, profile, k=0, name="x", gz=True):
         f.write("\n")
 
 
+def adversarial_phy(path, kind, n, seed):
+    """A Phylip file (gzip, no time stamp) of tools/synth.py's adversarial
+    matrix `kind`, cells written %.17g so that the double survives the text:
+    tokens in exponent form (1e-05, 8.6736173798840355e-19) and of 17 digits,
+    which the parsers read with strtod's rounding.  Returns the matrix's
+    largest cell."""
+    sys.path.insert(0, ROOT)
+    from tools.synth import ADVERSARIAL
+    D = ADVERSARIAL[kind](n, seed)
+    rows = ["%10d\n" % n]
+    k = 0
+    for i in range(n):
+        rows.append("\t".join([f"{kind[0]}{i}"] + ["%.17g" % v for v in D[k:k + i]]) + "\n")
+        k += i
+    with open(path, "wb") as raw, gzip.GzipFile(filename="", fileobj=raw, mode="wb", mtime=0) as f:
+        f.write("".join(rows).encode())
+    return float(D.max())
+
+
 def run(args, out):
     p = subprocess.run([REF] + args, capture_output=True, check=True)
     with open(out, "wb") as f:
@@ -386,6 +405,26 @@ def main():
             case(f"kma_{prof}_{m}_s", base + ["-d", m, "-s", "10"], f"kma_{prof}_{m}_s.out", "kma")
             case(f"kma_{prof}_{m}_b", base + ["-d", m, "-b", "0.5"], f"kma_{prof}_{m}_b.out", "kma")
             case(f"kma_{prof}_{m}_W", base + ["-d", m, "-W", "1000"], f"kma_{prof}_{m}_W.out", "kma")
+
+    # (viii) adversarial distance matrices (tools/synth.py ADVERSARIAL, n = 150):
+    # cells over many binades, dyadic ties, zero cells and identical rows, few
+    # distinct values.  -x: the reference's formNode sizes its buffer
+    # len1 + len2 + 32 (nwck.c:53) and prints two lengths of d + 1 + x bytes
+    # with 6 bytes of punctuation, so x = 12 - d is the highest precision it
+    # takes without writing past the buffer, d the digits before the point of
+    # the largest cell (no limb is longer).
+    for kind in ("additive", "line", "dyadic", "dupes", "grid"):
+        fn = f"adv_{kind}.phy.gz"
+        top = adversarial_phy(fn, kind, 150, seed=7)
+        x = str(12 - len(str(int(top))))
+        for m in ("nj", "dnj", "hnj"):
+            case(f"adv_{kind}_{m}", ["tree", "-i", fn, "-m", m, "-x", x], f"adv_{kind}_{m}.out", "tree")
+    for kind in ("line", "dyadic"):
+        case(f"adv_{kind}_p", ["tree", "-i", f"adv_{kind}.phy.gz", "-p", "-x", "9"], f"adv_{kind}_p.out", "tree")
+    # grid's cells are k / 100: scaled by 100 they are exact integers
+    case("adv_grid_s", ["tree", "-i", "adv_grid.phy.gz", "-s", "100"], "adv_grid_s.out", "tree")
+    case("adv_grid_hnj_s", ["tree", "-i", "adv_grid.phy.gz", "-m", "hnj", "-s", "100"], "adv_grid_hnj_s.out", "tree")
+    case("adv_grid_nj_b", ["tree", "-i", "adv_grid.phy.gz", "-m", "nj", "-b", "100"], "adv_grid_nj_b.out", "tree")
 
     with open("golden.json", "w") as f:
         json.dump({"reference": "ccphylo 0.8.5 (oracle/_ref/ccphylo, built by oracle/Makefile)",

@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """Generates the golden vectors of the tree methods upgma, cf, ff and mn by
 running the REFERENCE ccphylo binary built by oracle/Makefile
-(oracle/_ref/ccphylo) on the inputs gen_golden.py committed (no new inputs):
+(oracle/_ref/ccphylo) on the inputs gen_golden.py committed (no new inputs;
+run gen_golden.py first):
 
     make -C oracle && python tests/golden/gen_golden_linkage.py
 
 Outputs (data, committed): golden_linkage.json lists the cases with their
 command lines and md5; golden_linkage_out.tar.gz holds the outputs lk_*.out
-(453 KB of Newick text; the tests read the members).  cf has no cases on
+(453 KB of Newick text; the tests read the members), and
+golden_linkage_adv_out.tar.gz those of the adversarial matrices adv_*.phy.gz
+(an archive of their own: the first one stays as it is).  cf has no cases on
 matrices with missing cells (its update in the reference miscounts there; the
 engine refuses them)."""
 import gzip
@@ -48,6 +51,19 @@ def main():
         for m in ("upgma", "cf", "ff", "mn"):
             for name, inp, extra in variants + ([] if m == "cf" else missing):
                 args = ["tree", "-i", inp, "-m", m] + extra
+                out = f"lk_{name}_{m}.out"
+                cases.append({"name": f"{name}_{m}", "kind": "tree", "method": m, "args": args, "out": out,
+                              "md5": run(args, out, tar)})
+    # the adversarial matrices, at the -x of their golden.json cases (gen_golden.py (viii)); none has missing cells
+    with open("golden.json") as f:
+        xs = {c["args"][2]: c["args"][-1] for c in json.load(f)["cases"] if c["name"].startswith("adv_")
+              and c["name"].endswith("_dnj")}
+    with open("golden_linkage_adv_out.tar.gz", "wb") as raw, gzip.GzipFile(fileobj=raw, mode="wb", mtime=0) as gz, \
+            tarfile.open(fileobj=gz, mode="w") as tar:
+        for m in ("upgma", "cf", "ff", "mn"):
+            for inp in sorted(xs):
+                name = inp[:-len(".phy.gz")]
+                args = ["tree", "-i", inp, "-m", m, "-x", xs[inp]]
                 out = f"lk_{name}_{m}.out"
                 cases.append({"name": f"{name}_{m}", "kind": "tree", "method": m, "args": args, "out": out,
                               "md5": run(args, out, tar)})

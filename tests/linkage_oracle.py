@@ -87,11 +87,13 @@ def parse_tree_args(args):
 
 # ---------------------------------------------------------------- inputs
 def golden_out(case):
-    """The reference's bytes of a golden_linkage.json case (a member of golden_linkage_out.tar.gz)."""
+    """The reference's bytes of a golden_linkage.json case (a member of golden_linkage_out.tar.gz or, for the
+    adversarial matrices, of golden_linkage_adv_out.tar.gz)."""
     if not _OUT:
-        with tarfile.open(os.path.join(HERE, "golden", "golden_linkage_out.tar.gz")) as t:
-            for m in t.getmembers():
-                _OUT[m.name] = t.extractfile(m).read()
+        for arc in ("golden_linkage_out.tar.gz", "golden_linkage_adv_out.tar.gz"):
+            with tarfile.open(os.path.join(HERE, "golden", arc)) as t:
+                for m in t.getmembers():
+                    _OUT[m.name] = t.extractfile(m).read()
     return _OUT[case["out"]]
 
 

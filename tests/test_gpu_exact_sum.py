@@ -47,12 +47,25 @@ def _case(kind, n, rng):
         c = rng.random(n)
         c[rng.random(n) < 0.3] = 0.0
         c[: n // 10] = 0.0
+    elif kind == "clamped":   # wide-range values, 30 % exact zeros in runs (updateD's clamp on a non-metric matrix)
+        c = rng.random(n) * 10.0 ** rng.integers(-6, 6, n)
+        runs = np.repeat(rng.random(n // 8 + 1) < 0.3, 8)[:n]
+        c[runs] = 0.0
+    elif kind == "residue":   # O(1) values among O(1e-17) rounding residues (points on a line)
+        c = np.where(rng.random(n) < 0.5, rng.random(n), rng.random(n) * 1e-17)
+    elif kind == "low":       # the lowest normal exponents
+        c = np.ldexp(rng.random(n), -1008)
+    elif kind == "high":
+        c = np.ldexp(rng.random(n), 900)
     else:   # "integers": provable in any order, still through the same code
         c = rng.integers(0, 5000, n).astype(np.float64)
     return c
 
 
-@pytest.mark.parametrize("kind", ["uniform", "phylip", "dyadic", "wide", "zeros", "integers"])
+RECORDED_ONLY = ("clamped", "residue", "low", "high")   # nothing derives their parallel share
+
+
+@pytest.mark.parametrize("kind", ["uniform", "phylip", "dyadic", "wide", "zeros", "integers", *RECORDED_ONLY])
 def test_exact_sum_matches_serial(dev, kind):
     rng = np.random.default_rng(abs(hash(kind)) % 2 ** 32)
     par_used = 0
@@ -62,8 +75,12 @@ def test_exact_sum_matches_serial(dev, kind):
             c = _case(kind, n, rng)
             got, par = dev.selftest_row_sum(c)
             want = _serial(c)
-            assert got == want and math.copysign(1, got) == math.copysign(1, want), (kind, n, rep, got, want)
+            assert got == want and math.copysign(1, got) == math.copysign(1, want), \
+                (kind, n, rep, got, want, "par so far", par_used)
             par_used += par
+    print(f"exact-sum selftest {kind}: parallel form carried {par_used} of {3 * len(sizes)}")
+    if kind in RECORDED_ONLY:
+        return
     # the parallel form must carry ordinary inputs (the chain is the rare
     # fallback); dyadic inputs at large n hold more half-ulp ties than the
     # tie list (XS_CAP) and fall back by design

@@ -140,6 +140,74 @@ def staircase_packed(L, q, s, seed=5, holes=0.02):
     return seqs, incs, int(bits.sum())
 
 
+def _lt(M):
+    """Packed LT (cell (i, j), j < i, at i (i - 1) / 2 + j) of a square matrix."""
+    i, j = np.tril_indices(M.shape[0], -1)
+    return np.ascontiguousarray(M[i, j], dtype=np.float64)
+
+
+def adv_additive(n, seed):
+    """Attacks the exact row sum's binade walk and the Q tie rules: path lengths in a random binary tree whose
+    branches are 10**U(-6, 6), so every cherry ties in Q but for rounding and a row's contributions span many
+    binades."""
+    rng = np.random.default_rng(seed)
+    M = np.zeros((n, n))
+    depth = np.zeros(n)                       # leaf to the root of its present cluster
+    clusters = [np.array([t]) for t in range(n)]
+    while len(clusters) > 1:
+        a, b = rng.choice(len(clusters), 2, replace=False)
+        A, B = clusters[a], clusters[b]
+        la, lb = 10.0 ** rng.uniform(-6, 6, 2)
+        depth[A] += la
+        depth[B] += lb
+        d = depth[A][:, None] + depth[B][None, :]
+        M[np.ix_(A, B)] = d
+        M[np.ix_(B, A)] = d.T
+        clusters[min(a, b)] = np.concatenate((A, B))
+        clusters.pop(max(a, b))
+    return _lt(M)
+
+
+def adv_line(n, seed):
+    """Attacks updateD's clamp to zero and zero limbs: |x_i - x_j| of shuffled points on a line at scales 1e-3 ..
+    1e3, where (D_ik + D_kj - D_ij) / 2 is exactly 0 or a rounding residue for most k."""
+    rng = np.random.default_rng(seed)
+    x = rng.random(n) * 10.0 ** rng.integers(-3, 4, n)
+    x = rng.permutation(x)
+    return _lt(np.abs(x[:, None] - x[None, :]))
+
+
+def adv_dyadic(n, seed):
+    """Attacks the row sum's order-independence shortcut and half-ulp ties: cells (0..8) * 2**-(0..60), non-metric,
+    so no power of two bounds a row's sum under 2^53 units and many contributions are negative before the clamp."""
+    rng = np.random.default_rng(seed)
+    m = n * (n - 1) // 2
+    return rng.integers(0, 9, m) * np.ldexp(1.0, -rng.integers(0, 61, m))
+
+
+def adv_dupes(n, seed):
+    """Attacks the index tie rules: Euclidean distances of n points drawn with replacement from n // 8 distinct
+    ones, so cells are zero, rows are identical and Q ties exactly."""
+    rng = np.random.default_rng(seed)
+    pts = rng.random((max(n // 8, 1), 8))[rng.integers(0, max(n // 8, 1), n)]
+    sq = np.zeros((n, n))
+    for k in range(pts.shape[1]):   # one dimension at a time: no n x n x dim array
+        t = pts[:, k][:, None] - pts[:, k][None, :]
+        sq += t * t
+    return _lt(np.sqrt(sq))
+
+
+def adv_grid(n, seed):
+    """Attacks minQpair's replay table: cells (1..100) / 100, few distinct values and non-metric, so tens of rows
+    qualify for a rescan at every join."""
+    rng = np.random.default_rng(seed)
+    return rng.integers(1, 101, n * (n - 1) // 2) / 100.0
+
+
+ADVERSARIAL = {"additive": adv_additive, "line": adv_line, "dyadic": adv_dyadic, "dupes": adv_dupes,
+               "grid": adv_grid}
+
+
 def staircase_prefix(incs, L):
     """C[x] = included positions < x of a packed include mask, x = 0..L (int64)."""
     incs = np.ascontiguousarray(incs, dtype=np.uint32)
