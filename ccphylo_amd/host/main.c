@@ -1,5 +1,5 @@
 /*
- * main.c -- `ccphylo dist` and `ccphylo tree`, the stable CLI surface, with
+ * main.c -- `ccphylo dist`, `ccphylo tree` and `ccphylo dbscan`, the stable CLI surface, with
  * the hot path on the GPU engine (include/ccphylo_amd.h).
  *
  * Mirrors ref main.c:99 (dispatch), dist.c:473 main_dist / :42 makeMatrix /
@@ -14,7 +14,9 @@
  * `--device N` selects the GPU; `tree --gpus G [--transport rccl|host]`
  * shards the matrix over G ranks (host/mgpu.c); `dist --tree FILE` runs
  * dist and the tree in HBM without the Phylip text (`-m`, `--gpus`,
- * `--transport`, `--fast_sums` as for tree).
+ * `--transport`, `--fast_sums` as for tree); `dist --dbscan FILE
+ * [--max_distance E] [--min_neighbors N]` clusters that LT in HBM the same way
+ * (alone, or before --tree).
  */
 #include <ctype.h>
 #include <errno.h>
@@ -315,6 +317,145 @@ static int main_tree(int argc, char **argv) {
 	return err ? 1 : 0;
 }
 
+/* ============================================================== dbscan */
+static int dbscan_help(FILE *out) {
+	fprintf(out, "#CCPhylo make a DBSCAN given a set of phylip distance matrices.\n");
+	fprintf(out, "#   %-24s\t%-32s\t%s\n", "Options are:", "Desc:", "Default:");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'i', "input", "Input file", "stdin");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'o', "output", "Output file", "stdout");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'S', "separator", "Separator", "\\t");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'q', "quotes", "Quote taxa", "\\0");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'N', "min_neighbors", "Minimum neighbors", "1");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'e', "max_distance", "Maximum distance", "10.0");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'p', "float_precision", "Float precision on distance matrix", "double");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 's', "short_precision", "Short precision on distance matrix", "double / 1e0");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'b', "byte_precision", "Byte precision on distance matrix", "double / 1e0");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'H', "mmap", "Allocate matrix on the disk", "False");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'T', "tmp", "Set directory for temporary files", "");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'h', "help", "Shows this helpmessage", "");
+	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "device", "GPU", "0");
+	return out == stderr;
+}
+
+static double opt_dnum(Args *A, const char *attached, const char *opt) {
+	char *v = opt_value(A, attached, opt), *e;
+	double x = strtod(v, &e);
+	if(*e) die_opt("Invalid", opt);
+	return x;
+}
+
+/* dbscan.c:267 main_dbscan / :181 make_dbscan: every matrix of the input
+ * through ccg_dbscan, printed by ccq_print_dbscan */
+static int main_dbscan(int argc, char **argv) {
+	const char *in = "-", *outname = "-";
+	int et = 8, device = 0, minN = 1;
+	char sep = '\t', quotes = 0;
+	double bs = 1.0, maxDist = 10.0;
+	Args A = {argc, 0, argv};
+	for(A.k = 1; A.k < argc; ++A.k) {
+		char *a = argv[A.k];
+		if(a[0] != '-' || a[1] == 0) {
+			in = a;
+			if(A.k + 1 < argc) {
+				fprintf(stderr, "Unexpected non-option argument(s).\n");
+				return 1;
+			}
+			break;
+		}
+		if(a[1] == '-') {
+			char *name = a + 2, *eq = strchr(name, '=');
+			char *att = NULL;
+			if(eq) {
+				*eq = 0;
+				att = eq + 1;
+			}
+			if(*name == 0) { continue; }
+			else if(!strcmp(name, "input")) in = opt_value(&A, att, "input");
+			else if(!strcmp(name, "output")) outname = opt_value(&A, att, "output");
+			else if(!strcmp(name, "separator")) sep = opt_value(&A, att, "separator")[0];
+			else if(!strcmp(name, "quotes")) quotes = opt_value(&A, att, "quotes")[0];
+			else if(!strcmp(name, "min_neighbors")) minN = (int) opt_num(&A, att, "min_neighbors");
+			else if(!strcmp(name, "max_distance")) maxDist = opt_dnum(&A, att, "max_distance");
+			else if(!strcmp(name, "float_precision")) et = 4;
+			else if(!strcmp(name, "short_precision")) { et = 2; bs = opt_dvalue_def(&A, att, bs, "short_precision"); }
+			else if(!strcmp(name, "byte_precision")) { et = 1; bs = opt_dvalue_def(&A, att, bs, "byte_precision"); }
+			else if(!strcmp(name, "mmap")) { /* host memory knob: no effect on HBM */ }
+			else if(!strcmp(name, "tmp")) (void) opt_value(&A, att, "tmp");
+			else if(!strcmp(name, "device")) device = (int) opt_num(&A, att, "device");
+			else if(!strcmp(name, "help")) return dbscan_help(stdout);
+			else die_opt("Unknown", a);
+			continue;
+		}
+		for(char *p = a + 1; *p; ++p) {
+			char o = *p, *att = p + 1;
+			int took = 1;
+			switch(o) {
+				case 'i': in = opt_value(&A, att, "i"); break;
+				case 'o': outname = opt_value(&A, att, "o"); break;
+				case 'S': sep = opt_value(&A, att, "S")[0]; break;
+				case 'q': quotes = opt_value(&A, att, "q")[0]; break;
+				case 'N': minN = (int) opt_num(&A, att, "N"); break;
+				case 'e': maxDist = opt_dnum(&A, att, "e"); break;
+				case 'T': (void) opt_value(&A, att, "T"); break;
+				case 's': et = 2; bs = opt_dvalue_def(&A, att, bs, "s"); break;
+				case 'b': et = 1; bs = opt_dvalue_def(&A, att, bs, "b"); break;
+				case 'p': et = 4; took = 0; break;
+				case 'H': took = 0; break;
+				case 'h': return dbscan_help(stdout);
+				default: {
+					char bad[3] = {'-', o, 0};
+					die_opt("Unknown", bad);
+				}
+			}
+			if(took) break;
+		}
+	}
+	if((et == 2 || et == 1) && bs == 0) die_opt("Invalid", et == 2 ? "\"--short_precision\"" : "\"--byte_precision\"");
+	FILE *out = (outname[0] == '-' && outname[1] == 0) ? stdout : fopen(outname, "wb");
+	if(!out) {
+		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
+		return errno ? errno : 1;
+	}
+	ccq_reader *r = ccq_open(in);
+	if(!r) {
+		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
+		return errno ? errno : 1;
+	}
+	ccg_ctx *ctx = NULL;
+	ccq_ltd *D = ccq_ltd_new(32, et, bs);
+	ccq_names *T = ccq_names_new(32, 4);
+	int32_t *N = NULL;
+	char **names = NULL;
+	int err = 0, n, cap = 0;
+	while((n = ccq_load_phy(r, D, T, sep, quotes, &err)) > 0) {
+		if(cap < n) {
+			cap = n;
+			N = realloc(N, 2 * (size_t) cap * sizeof(int32_t));
+			names = realloc(names, (size_t) cap * sizeof(char *));
+		}
+		if(!ctx) ctx = open_gpu(device);
+		ccg_dbscan_args da = {n, et, bs, maxDist, minN};
+		int nclust = 0;
+		int rc = ccg_dbscan(ctx, &da, D->mat, N, N + cap, &nclust, NULL);
+		if(rc) {
+			fprintf(stderr, "ccphylo_amd: dbscan failed: %s\n", ccg_strerror(rc));
+			return 1;
+		}
+		for(int i = 0; i < n; ++i) names[i] = (char *) T->names[i]->seq;
+		ccq_print_dbscan(out, T->header->len ? (char *) T->header->seq : NULL, names, N, N + cap, n, nclust, maxDist,
+		                 minN);
+	}
+	if(out != stdout) fclose(out);
+	else fflush(stdout);
+	ccq_close(r);
+	ccq_ltd_free(D);
+	ccq_names_free(T);
+	free(N);
+	free(names);
+	if(ctx) ccg_destroy(ctx);
+	return err ? 1 : 0;
+}
+
 /* ================================================================ dist */
 static int dist_help(FILE *out) {
 	fprintf(out, "#CCPhylo dist calculates distances between samples based on overlaps between nucleotide count matrices created by e.g. KMA.\n");
@@ -335,6 +476,9 @@ static int dist_help(FILE *out) {
 	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 't', "threads", "Number of threads", "1");
 	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'h', "help", "Shows this helpmessage", "");
 	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "tree", "Also build the tree in HBM, Newick to FILE", "off");
+	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "dbscan", "Also cluster in HBM, table to FILE", "off");
+	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "max_distance", "dbscan -e for --dbscan", "10.0");
+	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "min_neighbors", "dbscan -N for --dbscan", "1");
 	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "tree_method", "nj / cf / ff / mn / hnj / dnj for --tree", "dnj");
 	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "tree_flag", "tree -f flags for --tree", "0");
 	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "gpus", "Shard --tree over G GPUs", "1");
@@ -606,7 +750,8 @@ static int dist_fsa_files(char **files, int nfiles, const char *tmpl, const char
  * them (ccq_names_set). */
 static int dist_tree(const char *in, const char *treename, const char *tmethod, int tflag, unsigned flag,
                      unsigned norm, unsigned minLength, double minCov, unsigned proxi, int precision, int et,
-                     double bs, unsigned threads, int device, int gpus, int transport, int fast) {
+                     double bs, unsigned threads, int device, int gpus, int transport, int fast,
+                     const char *dbname, double maxDist, int minN) {
 	int m;
 	if(!strcmp(tmethod, "dnj")) m = CCG_TREE_DNJ;
 	else if(!strcmp(tmethod, "nj")) m = CCG_TREE_NJ;
@@ -622,13 +767,24 @@ static int dist_tree(const char *in, const char *treename, const char *tmethod, 
 		fprintf(stderr, "ccphylo_amd: --gpus with --tree_method %s is not supported: the sharded engine runs nj, dnj and hnj.\n", tmethod);
 		return 1;
 	}
-	if(norm && (et == 2 || et == 1)) {
+	if(treename && norm && (et == 2 || et == 1)) {
 		/* the pipeline's text round trip of -W cells through dtouc is not restated */
 		fprintf(stderr, "ccphylo_amd: -W with -s / -b and --tree: use `ccphylo dist ... | ccphylo tree`.\n");
 		return 1;
 	}
-	FILE *tout = (treename[0] == '-' && treename[1] == 0) ? stdout : fopen(treename, "wb");
-	if(!tout) {
+	if(dbname && gpus > 1) {
+		fprintf(stderr, "ccphylo_amd: --gpus with --dbscan is not supported: the clustering runs on one GPU.\n");
+		return 1;
+	}
+	if(dbname && (et == 2 || et == 1) && (norm || bs != 1.0)) {
+		/* scaled or -W cells: the pipeline's text round trip through dtouc is not restated */
+		fprintf(stderr, "ccphylo_amd: -s / -b with a scale or -W and --dbscan is not supported: use `ccphylo dist ... | ccphylo dbscan`.\n");
+		return 1;
+	}
+	FILE *tout = NULL, *dout = NULL;
+	if(treename) tout = (treename[0] == '-' && treename[1] == 0) ? stdout : fopen(treename, "wb");
+	if(dbname) dout = (dbname[0] == '-' && dbname[1] == 0) ? stdout : fopen(dbname, "wb");
+	if((treename && !tout) || (dbname && !dout)) {
 		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
 		return 1;
 	}
@@ -638,15 +794,20 @@ static int dist_tree(const char *in, const char *treename, const char *tmethod, 
 		return 1;
 	}
 	if(ccq_peek(r) != '>') {
-		fprintf(stderr, "ccphylo_amd: --tree needs an MSA (FASTA) input.\n");
+		fprintf(stderr, "ccphylo_amd: --tree / --dbscan need an MSA (FASTA) input.\n");
 		return 1;
 	}
 	ccq_msa *M = ccq_load_msa_par(r, flag, minLength, minCov, proxi, threads > 16 ? (int) threads : 16, stderr);
 	ccq_close(r);
 	const int n = M->n;
-	if(n < 3) {
+	if(treename && n < 3) {
 		fprintf(stderr, "ccphylo_amd: --tree needs at least 3 included sequences (%d).\n", n);
 		return 1;
+	}
+	if(n < 2) {   /* `dist` prints no matrix, `dbscan` no table */
+		if(dout != stdout) fclose(dout);
+		ccq_msa_free(M);
+		return 0;
 	}
 	if(!M->pair) fprintf(stderr, "# %d / %d bases included in distance matrix.\n", ccq_npos(M->incs, M->len), M->len);
 	ccg_snp_args sa;
@@ -664,6 +825,9 @@ static int dist_tree(const char *in, const char *treename, const char *tmethod, 
 	sa.byteScale = bs;
 	ccg_tree_args ta = {n, et, bs, m, tflag, !fast, 0, 0};
 	ccg_join *joins = malloc((size_t) n * sizeof(ccg_join));
+	ccg_dbscan_args da = {n, et, bs, maxDist, minN};
+	int32_t *dbN = dbname ? malloc(2 * (size_t) n * sizeof(int32_t)) : NULL;
+	int nclust = 0;
 	int nj = 0, fn = 0, inc = 0;
 	double fd = 0;
 	/* -W distances are not integral: the Phylip text of `dist | tree` rounds
@@ -684,7 +848,10 @@ static int dist_tree(const char *in, const char *treename, const char *tmethod, 
 			snprintf(emsg, sizeof(emsg), "ccg_snp_ltd_shard: %s", ccg_strerror(rc));
 		else if(rp >= 0 && (rc = ccg_round_decimal_dev(ctx, dD, (int64_t) n * (n - 1) / 2, et, rp)))
 			snprintf(emsg, sizeof(emsg), "ccg_round_decimal_dev: %s", ccg_strerror(rc));
-		else if((rc = ccg_tree_dev(ctx, &ta, dD, joins, &nj, &fn, &fd, NULL)))
+		/* round, then cluster, then the tree: it consumes the buffer, ccg_dbscan_dev only reads it */
+		else if(dbname && (rc = ccg_dbscan_dev(ctx, &da, dD, dbN, dbN + n, &nclust, NULL)))
+			snprintf(emsg, sizeof(emsg), "ccg_dbscan_dev: %s", ccg_strerror(rc));
+		else if(treename && (rc = ccg_tree_dev(ctx, &ta, dD, joins, &nj, &fn, &fd, NULL)))
 			snprintf(emsg, sizeof(emsg), "ccg_tree_dev: %s", ccg_strerror(rc));
 		if(dD) ccg_free(ctx, dD);
 		ccg_destroy(ctx);
@@ -696,16 +863,27 @@ static int dist_tree(const char *in, const char *treename, const char *tmethod, 
 			                "their updateD rules run on one GPU: use --gpus 1.\n");
 	}
 	if(rc) {
-		fprintf(stderr, "ccphylo_amd: dist --tree failed: %s\n", emsg);
+		fprintf(stderr, "ccphylo_amd: dist --%s failed: %s\n", treename ? "tree" : "dbscan", emsg);
 		return 1;
 	}
-	fprintf(stderr, "# Total time used computing distances and tree: %.2f s.\n", (double) (clock() - t0) / 1000000);
+	fprintf(stderr, "# Total time used computing distances and %s: %.2f s.\n", treename ? "tree" : "clusters",
+	        (double) (clock() - t0) / 1000000);
 	ccq_names *T = ccq_names_new(32, 4);   /* as tree.c:61-66 */
 	ccq_names_set(T, M->headers, n, flag, '\t');
-	ccq_replay_newick(T, n, (const ccq_join *) joins, nj, fn, fd, tflag, precision);
-	fprintf(tout, "%s;\n", (char *) T->names[0]->seq);
-	if(tout != stdout) fclose(tout);
-	else fflush(stdout);
+	if(dbname) {   /* before the replay, which edits the names */
+		char **names = malloc((size_t) n * sizeof(char *));
+		for(int i = 0; i < n; ++i) names[i] = (char *) T->names[i]->seq;
+		ccq_print_dbscan(dout, NULL, names, dbN, dbN + n, n, nclust, maxDist, minN);
+		free(names);
+		if(dout != stdout) fclose(dout);
+		free(dbN);
+	}
+	if(treename) {
+		ccq_replay_newick(T, n, (const ccq_join *) joins, nj, fn, fd, tflag, precision);
+		fprintf(tout, "%s;\n", (char *) T->names[0]->seq);
+		if(tout != stdout) fclose(tout);
+	}
+	fflush(stdout);
 	ccq_names_free(T);
 	free(joins);
 	ccq_msa_free(M);
@@ -713,7 +891,9 @@ static int dist_tree(const char *in, const char *treename, const char *tmethod, 
 }
 
 static int main_dist(int argc, char **argv) {
-	const char *outname = "-", *noutname = NULL, *treename = NULL, *tmethod = "dnj";
+	const char *outname = "-", *noutname = NULL, *treename = NULL, *tmethod = "dnj", *dbname = NULL;
+	double maxDist = 10.0;
+	int minN = 1;
 	char **files = NULL;
 	int nfiles = 0, precision = 9, et = 8, device = 0, gpus = 0, transport = CCQ_TRANSPORT_RCCL, fast = 0, tflag = 0;
 	unsigned flag = 1, norm = 0, minLength = 1, proxi = 0, minDepth = 15, threads = 1;
@@ -766,6 +946,9 @@ static int main_dist(int argc, char **argv) {
 			else if(!strcmp(name, "tmp")) (void) opt_value(&A, att, "tmp");
 			else if(!strcmp(name, "device")) device = (int) opt_num(&A, att, "device");
 			else if(!strcmp(name, "tree")) treename = opt_value(&A, att, "tree");
+			else if(!strcmp(name, "dbscan")) dbname = opt_value(&A, att, "dbscan");
+			else if(!strcmp(name, "max_distance")) maxDist = opt_dnum(&A, att, "max_distance");
+			else if(!strcmp(name, "min_neighbors")) minN = (int) opt_num(&A, att, "min_neighbors");
 			else if(!strcmp(name, "tree_method")) tmethod = opt_value(&A, att, "tree_method");
 			else if(!strcmp(name, "tree_flag")) tflag = (int) opt_num(&A, att, "tree_flag");
 			else if(!strcmp(name, "gpus")) gpus = (int) opt_num(&A, att, "gpus");
@@ -888,9 +1071,9 @@ static int main_dist(int argc, char **argv) {
 		fprintf(stderr, "ccphylo_amd: multi-file dist input is not implemented by the GPU engine (use one MSA).\n");
 		return 1;
 	}
-	if(treename) {
+	if(treename || dbname) {
 		return dist_tree(nfiles ? files[0] : "-", treename, tmethod, tflag, flag, norm, minLength, minCov, proxi,
-		                 precision, et, bs, threads, device, gpus, transport, fast);
+		                 precision, et, bs, threads, device, gpus, transport, fast, dbname, maxDist, minN);
 	}
 	FILE *out = (outname[0] == '-' && outname[1] == 0) ? stdout : fopen(outname, "wb");
 	if(!out) {
@@ -974,6 +1157,7 @@ static int main_help(FILE *out) {
 	fprintf(out, "# Usage: ccphylo <command> [options]\n");
 	fprintf(out, "#    %-16s\t%s\n", "dist", "all-pairs SNP distances of an MSA (GPU)");
 	fprintf(out, "#    %-16s\t%s\n", "tree", "NJ / DNJ trees from Phylip matrices (GPU)");
+	fprintf(out, "#    %-16s\t%s\n", "dbscan", "DBSCAN clusters from Phylip matrices (GPU)");
 	return out == stderr;
 }
 
@@ -984,7 +1168,8 @@ int main(int argc, char **argv) {
 	}
 	if(!strcmp(argv[1], "dist")) return main_dist(argc - 1, argv + 1);
 	if(!strcmp(argv[1], "tree")) return main_tree(argc - 1, argv + 1);
+	if(!strcmp(argv[1], "dbscan")) return main_dbscan(argc - 1, argv + 1);
 	if(!strcmp(argv[1], "-h") || !strcmp(argv[1], "--help")) return main_help(stdout);
-	fprintf(stderr, "ccphylo_amd: command \"%s\" is outside the GPU engine's scope (dist, tree).\n", argv[1]);
+	fprintf(stderr, "ccphylo_amd: command \"%s\" is outside the GPU engine's scope (dist, tree, dbscan).\n", argv[1]);
 	return 1;
 }

@@ -86,6 +86,11 @@ class TreeArgs(C.Structure):
     ]
 
 
+class DbscanArgs(C.Structure):
+    _fields_ = [("n", C.c_int), ("etype", C.c_int), ("byteScale", C.c_double), ("maxDist", C.c_double),
+                ("minN", C.c_int)]
+
+
 class Join(C.Structure):
     _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("Li", C.c_double), ("Lj", C.c_double)]
 
@@ -119,7 +124,7 @@ ENGINE_SYMBOLS = [
     "ccg_rccl_unique_id", "ccg_rccl_open", "ccg_rccl_close", "ccg_rccl_abort", "ccg_tree_shard", "ccg_tree_shard_dev",
     "ccg_kma_ltd", "ccg_kma_ltd_dev", "ccg_snp_ltd_shard_dev", "ccg_snp_ltd_shard", "ccg_selftest_row_sum",
     "ccg_round_decimal_dev", "ccg_last_dist_ms", "ccg_last_dist_plan", "ccg_tree_dev_state", "ccg_tree_shard_bytes", "ccg_ctx_configure",
-    "ccg_shutdown",
+    "ccg_shutdown", "ccg_dbscan", "ccg_dbscan_dev", "ccg_dbscan_count_dev",
 ]
 # every symbol of include/ccphylo_host.h
 HOST_SYMBOLS = [
@@ -129,6 +134,7 @@ HOST_SYMBOLS = [
     "ccq_replay_newick", "ccq_replay_newick_strings", "ccq_newick_pair",
     "ccq_code_table", "ccq_read_fasta", "ccq_pack", "ccq_init_inc", "ccq_inc_update", "ccq_npos",
     "ccq_load_msa", "ccq_load_msa_par", "ccq_msa_free", "ccq_load_fsa_files", "ccq_load_kma", "ccq_kma_free",
+    "ccq_print_dbscan",
 ]
 
 _engine = None
@@ -198,6 +204,10 @@ def engine_lib():
         lib.ccg_kma_ltd_dev.argtypes = lib.ccg_kma_ltd.argtypes
         lib.ccg_selftest_row_sum.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double),
                                              C.POINTER(C.c_int)]
+        lib.ccg_dbscan.argtypes = [C.c_void_p, C.POINTER(DbscanArgs), C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+        lib.ccg_dbscan_dev.argtypes = lib.ccg_dbscan.argtypes
+        lib.ccg_dbscan_count_dev.argtypes = [C.c_void_p, C.POINTER(DbscanArgs), C.c_void_p, C.c_void_p, C.c_void_p]
         _engine = lib
     return _engine
 
@@ -238,6 +248,9 @@ def host_lib():
         lib.ccq_load_kma.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_uint, C.c_uint, C.c_double, C.c_int,
                                      C.c_void_p]
         lib.ccq_kma_free.argtypes = [C.c_void_p]
+        lib.ccq_print_dbscan.restype = None
+        lib.ccq_print_dbscan.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_int, C.c_double, C.c_int]
         _host = lib
     return _host
 
@@ -406,6 +419,35 @@ class Device:
         rc = fn_(self.h, C.byref(a), C.c_void_p(dptr), joins.ctypes.data, C.byref(nj), C.byref(fn), C.byref(fd), st)
         self._check(rc, "ccg_tree")
         return joins[:nj.value], fn.value, fd.value, list(st)
+
+    def dbscan(self, D, n, max_dist=10.0, min_neighbors=1, etype=8, byte_scale=1.0):
+        """`ccphylo dbscan` on a packed host LT (ccg_dbscan).  Returns
+        (N, C, nclust, stats): neighbour counts, cluster ids (the smallest
+        member of each cluster) and the number of clusters."""
+        D = np.ascontiguousarray(D, dtype=ETYPES[etype])
+        assert D.size == n * (n - 1) // 2
+        return self._dbscan(self.lib.ccg_dbscan, D.ctypes.data if D.size else None, n, max_dist, min_neighbors, etype,
+                            byte_scale)
+
+    def dbscan_dev(self, dptr, n, max_dist=10.0, min_neighbors=1, etype=8, byte_scale=1.0):
+        """Same on a device LT (ccg_dbscan_dev); the buffer is left unmodified."""
+        return self._dbscan(self.lib.ccg_dbscan_dev, dptr, n, max_dist, min_neighbors, etype, byte_scale)
+
+    def _dbscan(self, fn_, ptr, n, max_dist, min_neighbors, etype, byte_scale):
+        N = np.zeros(max(n, 1), dtype=np.int32)
+        Cl = np.zeros(max(n, 1), dtype=np.int32)
+        nc = C.c_int(0)
+        st = (C.c_int64 * 4)()
+        a = DbscanArgs(n, etype, byte_scale, max_dist, min_neighbors)
+        rc = fn_(self.h, C.byref(a), C.c_void_p(ptr), N.ctypes.data, Cl.ctypes.data, C.byref(nc), st)
+        self._check(rc, "ccg_dbscan")
+        return N[:n], Cl[:n], nc.value, list(st)
+
+    def dbscan_count_dev(self, dptr, n, N_ptr, fany_ptr, max_dist=10.0, etype=8, byte_scale=1.0):
+        """Enqueues the count pass alone (ccg_dbscan_count_dev) into device arrays."""
+        a = DbscanArgs(n, etype, byte_scale, max_dist, 1)
+        self._check(self.lib.ccg_dbscan_count_dev(self.h, C.byref(a), C.c_void_p(dptr), C.c_void_p(N_ptr),
+                                                  C.c_void_p(fany_ptr)), "ccg_dbscan_count_dev")
 
     def tree_shard(self, D, n, coll=None, etype=8, byte_scale=1.0, method=CCG_TREE_NJ, flags=0, exact=True,
                    profile=False, max_joins=0):
@@ -852,4 +894,24 @@ def write_phylip(path, D, n, names, flag=1, precision=9, etype=8, byte_scale=1.0
     if not fp:
         raise OSError(path)
     lib.ccq_print_phy(fp, C.byref(ltd), arr, None, None, flag, precision)
+    libc.fclose(fp)
+
+
+def write_dbscan(path, names, N, Cl, nclust, max_dist=10.0, min_neighbors=1, header=None):
+    """Writes a clustering with the host writer (ccq_print_dbscan, ref dbscan.c:165)."""
+    lib = host_lib()
+    libc = C.CDLL(None)
+    libc.fopen.restype = C.c_void_p
+    libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
+    libc.fclose.argtypes = [C.c_void_p]
+    N = np.ascontiguousarray(N, dtype=np.int32)
+    Cl = np.ascontiguousarray(Cl, dtype=np.int32)
+    n = len(names)
+    assert N.size == n and Cl.size == n
+    arr = (C.c_char_p * max(n, 1))(*[s.encode() for s in names])
+    fp = libc.fopen(path.encode(), b"wb")
+    if not fp:
+        raise OSError(path)
+    lib.ccq_print_dbscan(fp, header.encode() if header else None, arr, N.ctypes.data, Cl.ctypes.data, n, int(nclust),
+                         float(max_dist), int(min_neighbors))
     libc.fclose(fp)

@@ -19,6 +19,9 @@
  *   ccg_tree_shard  the same loop with the LT rows split over ranks
  *                 (SURVEY.md 8(e)), one process per GPU, collectives over
  *                 RCCL (ccg_rccl_open) or a caller-supplied transport.
+ *   ccg_dbscan    replaces dbscan(D, N, C, maxDist, minN) (dbscan.c:31, called
+ *                 dbscan.c:217); print_dbscan (dbscan.c:165) is
+ *                 ccq_print_dbscan of include/ccphylo_host.h.
  *   ccg_tree      replaces dnj_thread(D, sD, Q, N, names, t) (dnj.c:1054,
  *                 called tree.c:89) and nj_thread(D, sD, N, names, t)
  *                 (nj.c:1612, called tree.c:91).  It returns the join list;
@@ -375,6 +378,46 @@ int ccg_snp_ltd_shard(ccg_ctx *ctx, const ccg_snp_args *a, int rank, int world, 
  * would round.  CCG_EUNSUP for etype 2/1, or for a cell with more significant
  * digits than a double holds at that precision. */
 int ccg_round_decimal_dev(ccg_ctx *ctx, void *D_dev, int64_t elems, int etype, int precision);
+
+/* ------------------------------------------------------------------ */
+/* dbscan: clusters at a distance threshold on a packed LT matrix      */
+/* ------------------------------------------------------------------ */
+/* Replaces dbscan(D, N, C, maxDist, minN) (dbscan.c:31, called dbscan.c:217).
+ * A cell d(i,j) (etype 2 / 1: cell / byteScale) is a neighbour pair when
+ * d <= maxDist compared as doubles -- so is a missing cell (-1) whenever
+ * maxDist >= -1, as in the reference.  N[i] counts the neighbours of i,
+ * C[i] is the cluster of i named by its smallest member, *nclust the number
+ * of i with C[i] == i; all are integers, bit-identical to the reference. */
+typedef struct {
+	int n;                 /* taxa (>= 1) */
+	int etype;             /* 8, 4, 2, 1 */
+	double byteScale;
+	double maxDist;        /* -e */
+	int minN;              /* -N: a row with minN <= N[i] is a core row; may be <= 0 */
+} ccg_dbscan_args;
+
+/* D: host LT (n(n-1)/2 elements; ignored for n = 1), left unmodified.  N, C:
+ * host arrays of n entries.  stats (may be NULL, 4 entries): [0] border rows
+ * (0 < N[i] < minN) searched for a core neighbour, [1] cells loaded over all
+ * passes (n(n-1)/2 when there is no border row: the LT is read once),
+ * [2] kernel launches, [3] device time in microseconds.  n = 1 launches
+ * nothing (N = {0}, C = {0}, *nclust = 1).  CCG_EINVAL for n < 1, an unknown
+ * etype, or etype 2 / 1 with byteScale 0. */
+int ccg_dbscan(ccg_ctx *ctx, const ccg_dbscan_args *a, const void *D, int32_t *N, int32_t *C, int *nclust,
+               int64_t *stats);
+/* Same on a DEVICE LT buffer, with ccg_tree_dev's conventions (waits for the
+ * device first unless CCG_CTX_NOSYNC; runs on the context's stream).  D_dev is
+ * left unmodified: a caller can cluster first and then hand the same buffer to
+ * ccg_tree_dev, which consumes it. */
+int ccg_dbscan_dev(ccg_ctx *ctx, const ccg_dbscan_args *a, const void *D_dev, int32_t *N, int32_t *C, int *nclust,
+                   int64_t *stats);
+/* The first pass of ccg_dbscan_dev alone, enqueued on the context's stream
+ * without waiting for its end (benchmarks time it, tools/dbscan_bench.py; like
+ * the other *_dev calls it waits for the device first unless CCG_CTX_NOSYNC): one read
+ * of the LT (n >= 2) into DEVICE arrays of n ints, N_dev[i] the neighbour
+ * count and fany_dev[i] the smallest j < i with d(i,j) <= maxDist
+ * (0x7f7f7f7f where there is none). */
+int ccg_dbscan_count_dev(ccg_ctx *ctx, const ccg_dbscan_args *a, const void *D_dev, int32_t *N_dev, int32_t *fany_dev);
 
 /* ------------------------------------------------------------------ */
 /* device memory helpers (for callers that keep the pipeline in HBM)   */

@@ -4,6 +4,7 @@
  * These are the reference's I/O boundaries re-implemented (not copied) so
  * that `ccphylo dist` / `ccphylo tree` stay byte-compatible:
  *   - Phylip reader / writer            (ref phy.c:251 loadPhy, phy.c:59 printphy)
+ *   - dbscan table writer               (ref dbscan.c:165 print_dbscan)
  *   - Newick builder, replayed from the join list produced on the GPU
  *                                       (ref nwck.c:35 formNode, :79 formLastNode,
  *                                        :114 formLastBiNode, str.c:51 byteshift)
@@ -80,6 +81,13 @@ int ccq_load_phy(ccq_reader *r, ccq_ltd *D, ccq_names *T, char sep, char quotes,
  * relaxed names, bit 4 = comment line. */
 void ccq_print_phy(FILE *out, const ccq_ltd *D, char **names, const unsigned char *include,
                    const char *comment, unsigned format, int precision);
+
+/* ---- dbscan ---- */
+/* dbscan.c:165 print_dbscan, preceded by the "#header" line of dbscan.c:220
+ * when header is not NULL and not empty: "## n nclust maxDist minN", the
+ * column names, then name, neighbours and cluster of every sample. */
+void ccq_print_dbscan(FILE *out, const char *header, char **names, const int32_t *N, const int32_t *C, int n,
+                      int nclust, double maxDist, int minN);
 
 /* ---- Newick replay (GPU join list -> tree string) ---- */
 typedef struct {
