@@ -33,16 +33,20 @@ struct ccg_ctx {
 	char name[256];
 	float dist_ms;   // the last dist call's pair kernels (HIP events on the engine stream)
 	int dist_slices, dist_slice_words;   // its split-K plan (plan_split; 0, 0: no tile kernel ran)
+	float vec_ms;    // the last vec call's pre-pass and pair kernel (the same events)
+	int vec_pending; // ... still to be read from the events (a CCG_CTX_NOSYNC call)
+	int vec_tile;    // its tile edge (0: nothing launched)
 	int flags;       // CCG_CTX_* (ccg_ctx_configure)
 	int masked;      // the stream was created with a CU mask (ccg_ctx_configure)
 	int ncu, cus;    // the device's CUs; the CUs the stream may use (0: all)
 	// device workspaces kept across runs (grown on demand, freed by
 	// ccg_destroy): slots 0 / 1 the tree's, slot 2 the dist's bit planes in a
-	// CCG_CTX_NOSYNC context, slot 3 dbscan's per-row vectors.  A run then
+	// CCG_CTX_NOSYNC context, slot 3 dbscan's per-row vectors, slot 4 the vec
+	// pre-pass's per-row values.  A run then
 	// makes no hipFree, which waits for
 	// every stream of the device, so such a context never waits for another
-	void *ws[4];
-	size_t ws_bytes[4];
+	void *ws[5];
+	size_t ws_bytes[5];
 };
 // slot k of the context's workspace cache, at least `bytes` long
 int ccg_ctx_workspace(ccg_ctx *c, int k, size_t bytes, void **p);

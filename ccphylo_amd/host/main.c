@@ -1,6 +1,6 @@
 /*
- * main.c -- `ccphylo dist`, `ccphylo tree` and `ccphylo dbscan`, the stable CLI surface, with
- * the hot path on the GPU engine (include/ccphylo_amd.h).
+ * main.c -- `ccphylo dist`, `ccphylo tree`, `ccphylo dbscan` and `ccphylo tsv2phy`, the stable
+ * CLI surface, with the hot path on the GPU engine (include/ccphylo_amd.h).
  *
  * Mirrors ref main.c:99 (dispatch), dist.c:473 main_dist / :42 makeMatrix /
  * cdist.c:196 ltdMsaMatrix_get, and tree.c:146 main_tree / :37 formTree:
@@ -16,7 +16,8 @@
  * dist and the tree in HBM without the Phylip text (`-m`, `--gpus`,
  * `--transport`, `--fast_sums` as for tree); `dist --dbscan FILE
  * [--max_distance E] [--min_neighbors N]` clusters that LT in HBM the same way
- * (alone, or before --tree).
+ * (alone, or before --tree); `tsv2phy --tree FILE [--tree_method M]` hands
+ * the table's LT to the tree in HBM, and writes the Phylip text only with -o.
  */
 #include <ctype.h>
 #include <errno.h>
@@ -457,6 +458,27 @@ static int main_dbscan(int argc, char **argv) {
 }
 
 /* ================================================================ dist */
+/* --tree_method of the fused pipelines (dist --tree, tsv2phy --tree) -> CCG_TREE_*; -1 with a message */
+static int fused_tree_method(const char *tmethod) {
+	if(!strcmp(tmethod, "dnj")) return CCG_TREE_DNJ;
+	if(!strcmp(tmethod, "nj")) return CCG_TREE_NJ;
+	if(!strcmp(tmethod, "hnj")) return CCG_TREE_HNJ;
+	if(!strcmp(tmethod, "cf")) return CCG_TREE_CF;
+	if(!strcmp(tmethod, "ff")) return CCG_TREE_FF;
+	if(!strcmp(tmethod, "mn")) return CCG_TREE_MN;
+	fprintf(stderr, "ccphylo_amd: --tree_method %s: the fused pipeline runs nj, cf, ff, mn, hnj and dnj.\n", tmethod);
+	return -1;
+}
+
+/* the tail of a fused run: the engine's joins replayed over the names T holds
+ * (ccq_names_set), the Newick line written and the file closed */
+static void fused_write_newick(FILE *tout, ccq_names *T, int n, const ccg_join *joins, int nj, int fn, double fd,
+                               int tflag, int precision) {
+	ccq_replay_newick(T, n, (const ccq_join *) joins, nj, fn, fd, tflag, precision);
+	fprintf(tout, "%s;\n", (char *) T->names[0]->seq);
+	if(tout != stdout) fclose(tout);
+}
+
 static int dist_help(FILE *out) {
 	fprintf(out, "#CCPhylo dist calculates distances between samples based on overlaps between nucleotide count matrices created by e.g. KMA.\n");
 	fprintf(out, "#   %-24s\t%-32s\t%s\n", "Options are:", "Desc:", "Default:");
@@ -752,17 +774,8 @@ static int dist_tree(const char *in, const char *treename, const char *tmethod, 
                      unsigned norm, unsigned minLength, double minCov, unsigned proxi, int precision, int et,
                      double bs, unsigned threads, int device, int gpus, int transport, int fast,
                      const char *dbname, double maxDist, int minN) {
-	int m;
-	if(!strcmp(tmethod, "dnj")) m = CCG_TREE_DNJ;
-	else if(!strcmp(tmethod, "nj")) m = CCG_TREE_NJ;
-	else if(!strcmp(tmethod, "hnj")) m = CCG_TREE_HNJ;
-	else if(!strcmp(tmethod, "cf")) m = CCG_TREE_CF;
-	else if(!strcmp(tmethod, "ff")) m = CCG_TREE_FF;
-	else if(!strcmp(tmethod, "mn")) m = CCG_TREE_MN;
-	else {
-		fprintf(stderr, "ccphylo_amd: --tree_method %s: the fused pipeline runs nj, cf, ff, mn, hnj and dnj.\n", tmethod);
-		return 1;
-	}
+	const int m = fused_tree_method(tmethod);
+	if(m < 0) return 1;
 	if(gpus > 1 && (m == CCG_TREE_CF || m == CCG_TREE_FF || m == CCG_TREE_MN)) {
 		fprintf(stderr, "ccphylo_amd: --gpus with --tree_method %s is not supported: the sharded engine runs nj, dnj and hnj.\n", tmethod);
 		return 1;
@@ -878,11 +891,7 @@ static int dist_tree(const char *in, const char *treename, const char *tmethod, 
 		if(dout != stdout) fclose(dout);
 		free(dbN);
 	}
-	if(treename) {
-		ccq_replay_newick(T, n, (const ccq_join *) joins, nj, fn, fd, tflag, precision);
-		fprintf(tout, "%s;\n", (char *) T->names[0]->seq);
-		if(tout != stdout) fclose(tout);
-	}
+	if(treename) fused_write_newick(tout, T, n, joins, nj, fn, fd, tflag, precision);
 	fflush(stdout);
 	ccq_names_free(T);
 	free(joins);
@@ -1152,12 +1161,263 @@ static int main_dist(int argc, char **argv) {
 	return 0;
 }
 
+/* ============================================================= tsv2phy */
+static int tsv2phy_help(FILE *out) {
+	fprintf(out, "#CCPhylo tsv2phy converts tsv files to phylip distance files.\n");
+	fprintf(out, "#   %-24s\t%-32s\t%s\n", "Options are:", "Desc:", "Default:");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'i', "input", "Input file", "stdin");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'o', "output", "Output file", "stdout");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'S', "separator", "Separator", "\\t");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'x', "print_precision", "Floating point print precision", "9");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'd', "distance", "Distance method", "cos");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'D', "distance_help", "Help on option \"-d\"", "");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'f', "flag", "Output flags", "1");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'F', "flag_help", "Help on option \"-f\"", "");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'p', "float_precision", "Float precision on distance matrix", "False / double");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 's', "short_precision", "Short precision on distance matrix", "False / double / 1e0");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'b', "byte_precision", "Byte precision on distance matrix", "False / double / 1e0");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'H', "mmap", "Allocate matrix on the disk", "False");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'T', "tmp", "Set directory for temporary files", "");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'h', "help", "Shows this helpmessage", "");
+	return out == stderr;
+}
+
+/* -d of tsv2phy (tsv2phy.c:316-357) -> CCG_VEC_* and the exponent of l<n>;
+ * exits like the reference's invaArg where it refuses too */
+static int tsv_metric_id(const char *method, double *exponent) {
+	*exponent = 0;
+	if(!strcmp(method, "cos")) return CCG_VEC_COS;
+	if(!strcmp(method, "chi2")) return CCG_VEC_CHI2;
+	if(!strcmp(method, "bc")) return CCG_VEC_BC;
+	if(!strcmp(method, "l1")) return CCG_VEC_L1;
+	if(!strcmp(method, "l2")) return CCG_VEC_L2;
+	if(!strcmp(method, "linf")) return CCG_VEC_LINF;
+	if(*method == 'l') {
+		char *e;
+		*exponent = strtod(method + 1, &e);
+		if(*e != 0) {
+			fprintf(stderr, "Invalid value parsed at %s.\n", "\"--distance ln\"");
+			exit(1);
+		}
+		/* the reference takes "l", "l0" and "l-1" and prints pow(d, 1 / n) of them */
+		if(!(*exponent > 0) || *exponent * 0 != 0) {
+			fprintf(stderr, "ccphylo_amd: -d %s: the norm of l<n> must be finite and > 0.\n", method);
+			exit(1);
+		}
+		return CCG_VEC_LN;
+	}
+	if(!strcmp(method, "p")) return CCG_VEC_PEARSON;
+	fprintf(stderr, "Invalid value parsed at %s.\n", "\"--distance\"");
+	exit(1);
+}
+
+/* tsv2phy.c:154 main_tsv2phy / :35 tsv2phy: the table goes up once, the cells
+ * come from ccg_vec_ltd_dev and the LT stays in HBM: it is read back for the
+ * Phylip text, and with --tree FILE handed to ccg_tree_dev in place */
+static int main_tsv2phy(int argc, char **argv) {
+	const char *in = "-", *outname = NULL, *method = "cos", *treename = NULL, *tmethod = "dnj";
+	int flag = 1, precision = 9, vtype = 8, device = 0, scaled = 0;
+	char sep = '\t';
+	Args A = {argc, 0, argv};
+	for(A.k = 1; A.k < argc; ++A.k) {
+		char *a = argv[A.k];
+		if(a[0] != '-' || a[1] == 0) {
+			in = a;
+			if(A.k + 1 < argc) {
+				fprintf(stderr, "Too many non-option arguments handed.\n");
+				return 1;
+			}
+			break;
+		}
+		if(a[1] == '-') {
+			char *name = a + 2, *eq = strchr(name, '=');
+			char *att = NULL;
+			if(eq) {
+				*eq = 0;
+				att = eq + 1;
+			}
+			if(*name == 0) { continue; }
+			else if(!strcmp(name, "input")) in = opt_value(&A, att, "input");
+			else if(!strcmp(name, "output")) outname = opt_value(&A, att, "output");
+			else if(!strcmp(name, "separator")) sep = opt_value(&A, att, "separator")[0];
+			else if(!strcmp(name, "print_precision")) precision = (int) opt_num(&A, att, "print_precision");
+			else if(!strcmp(name, "distance")) method = opt_value(&A, att, "distance");
+			else if(!strcmp(name, "distance_help")) method = NULL;
+			else if(!strcmp(name, "flag")) flag = (int) opt_num(&A, att, "flag");
+			else if(!strcmp(name, "flag_help")) flag = -1;
+			else if(!strcmp(name, "float_precision")) vtype = 4;
+			else if(!strcmp(name, "short_precision")) { scaled = 1; (void) opt_dvalue_def(&A, att, 1.0, "short_precision"); }
+			else if(!strcmp(name, "byte_precision")) { scaled = 1; (void) opt_dvalue_def(&A, att, 1.0, "byte_precision"); }
+			else if(!strcmp(name, "mmap")) { /* host memory knob: no effect on HBM */ }
+			else if(!strcmp(name, "tmp")) (void) opt_value(&A, att, "tmp");
+			else if(!strcmp(name, "tree")) treename = opt_value(&A, att, "tree");
+			else if(!strcmp(name, "tree_method")) tmethod = opt_value(&A, att, "tree_method");
+			else if(!strcmp(name, "device")) device = (int) opt_num(&A, att, "device");
+			else if(!strcmp(name, "help")) return tsv2phy_help(stdout);
+			else {
+				fprintf(stderr, "Unknown argument or option: \"%s\"\n", a);
+				return 1;
+			}
+			continue;
+		}
+		for(char *p = a + 1; *p; ++p) {
+			char o = *p, *att = p + 1;
+			int took = 1;
+			switch(o) {
+				case 'i': in = opt_value(&A, att, "i"); break;
+				case 'o': outname = opt_value(&A, att, "o"); break;
+				case 'S': sep = opt_value(&A, att, "S")[0]; break;
+				case 'x': precision = (int) opt_num(&A, att, "x"); break;
+				case 'd': method = opt_value(&A, att, "d"); break;
+				case 'f': flag = (int) opt_num(&A, att, "f"); break;
+				case 'T': (void) opt_value(&A, att, "T"); break;
+				case 's': scaled = 1; (void) opt_dvalue_def(&A, att, 1.0, "s"); break;
+				case 'b': scaled = 1; (void) opt_dvalue_def(&A, att, 1.0, "b"); break;
+				case 'D': method = NULL; took = 0; break;
+				case 'F': flag = -1; took = 0; break;
+				case 'p': vtype = 4; took = 0; break;
+				case 'H': took = 0; break;
+				case 'h': return tsv2phy_help(stdout);
+				default: {
+					fprintf(stderr, "Unknown argument or option: \"-%c\"\n", o);
+					return 1;
+				}
+			}
+			if(took) break;
+		}
+	}
+	if(flag == -1) {
+		fprintf(stdout, "Format flags output format, add them to combine them.\n");
+		fprintf(stdout, "#\n");
+		fprintf(stdout, "# 1:\tRelaxed Phylip\n");
+		fprintf(stdout, "#\n");
+		return 0;
+	}
+	if(!method) {
+		fprintf(stdout, "# Distance calculation methods:\n");
+		fprintf(stdout, "#\n");
+		fprintf(stdout, "# cos:\tCalculate cosine distance between vectors.\n");
+		fprintf(stdout, "# chi2:\tCalculate the chi square distance\n");
+		fprintf(stdout, "# bc:\tCalculate the Bray-Curtis dissimilarity between vectors.\n");
+		fprintf(stdout, "# ln:\tCalculate distance between vectors as the n-norm distance between the count vectors. Replace \"n\" with the waned norm\n");
+		fprintf(stdout, "# linf:\tCalculate distance between vectors as the l_infinity distance between the count vectors.\n");
+		fprintf(stdout, "# p:\tCalculate Pearsons correlation between vectors.\n");
+		fprintf(stdout, "#\n");
+		return 0;
+	}
+	double exponent;
+	const int metric = tsv_metric_id(method, &exponent);
+	if(scaled) {
+		/* the reference's own short and byte rows are defective: tsv2phy.c:316-357
+		 * never sets distcmp_s, so -s computes cos whatever -d says; bc -b prints
+		 * all zeros and linf -b prints wrapped bytes (all three seen on a 7 x 5
+		 * table).  There is nothing to be compatible with */
+		fprintf(stderr, "ccphylo_amd: tsv2phy -s / -b is not supported: the reference's short and byte rows do not compute the chosen distance; use double or -p.\n");
+		return 1;
+	}
+	const int tm = treename ? fused_tree_method(tmethod) : 0;
+	if(tm < 0) return 1;
+	ccq_reader *r = ccq_open(in);
+	if(!r) {
+		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
+		return errno ? errno : 1;
+	}
+	/* with --tree the Phylip text is written only where -o asks for it */
+	if(!outname && !treename) outname = "-";
+	FILE *out = NULL, *tout = NULL;
+	if(outname) out = (outname[0] == '-' && outname[1] == 0) ? stdout : fopen(outname, "wb");
+	if(treename) tout = (treename[0] == '-' && treename[1] == 0) ? stdout : fopen(treename, "wb");
+	if((outname && !out) || (treename && !tout)) {
+		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
+		return errno ? errno : 1;
+	}
+	void *X = NULL;
+	int m = 0, n = 0;
+	char msg[256];
+	int rc = ccq_load_tsv(r, sep, vtype, &X, &m, &n, msg, sizeof(msg));
+	ccq_close(r);
+	if(rc) {
+		fprintf(stderr, "%s\n", msg);
+		return rc;
+	}
+	if(!m) {
+		fprintf(stderr, "Input matrix contained zero rows.\n");
+		return 0;
+	}
+	if(treename && m < 3) {
+		fprintf(stderr, "ccphylo_amd: --tree needs at least 3 rows (%d).\n", m);
+		return 1;
+	}
+	const size_t cells = (size_t) m * (size_t) (m - 1) / 2;
+	double *D = out ? malloc((cells ? cells : 1) * sizeof(double)) : NULL;
+	ccg_join *joins = treename ? malloc((size_t) m * sizeof(ccg_join)) : NULL;
+	if((out && !D) || (treename && !joins)) {
+		fprintf(stderr, "Error: out of host memory\n");
+		return 12;
+	}
+	int nj = 0, fn = 0;
+	double fd = 0;
+	if(m > 1) {   /* a one-row table has no cell: nothing to launch */
+		ccg_ctx *ctx = open_gpu(device);
+		void *dX = NULL, *dD = NULL;
+		char emsg[320] = "";
+		const size_t xb = (size_t) m * (size_t) n * (size_t) vtype;
+		ccg_vec_args va = {m, n, n, vtype, NULL, metric, exponent, 8};
+		ccg_tree_args ta = {m, 8, 1.0, tm, 0, 1, 0, 0};
+		if((rc = ccg_malloc(ctx, &dX, xb)) || (rc = ccg_malloc(ctx, &dD, cells * sizeof(double))))
+			snprintf(emsg, sizeof(emsg), "device buffers: %s", ccg_strerror(rc));
+		else if((rc = ccg_memcpy_h2d(ctx, dX, X, xb))) snprintf(emsg, sizeof(emsg), "upload: %s", ccg_strerror(rc));
+		else {
+			va.X = dX;
+			if((rc = ccg_vec_ltd_dev(ctx, &va, dD))) snprintf(emsg, sizeof(emsg), "ccg_vec_ltd_dev: %s", ccg_strerror(rc));
+			else if(out && (rc = ccg_memcpy_d2h(ctx, D, dD, cells * sizeof(double))))
+				snprintf(emsg, sizeof(emsg), "read back: %s", ccg_strerror(rc));
+			/* the text first: the tree consumes the buffer */
+			else if(treename && (rc = ccg_tree_dev(ctx, &ta, dD, joins, &nj, &fn, &fd, NULL)))
+				snprintf(emsg, sizeof(emsg), "ccg_tree_dev: %s", ccg_strerror(rc));
+		}
+		if(dX) ccg_free(ctx, dX);
+		if(dD) ccg_free(ctx, dD);
+		ccg_destroy(ctx);
+		if(rc) {
+			fprintf(stderr, "ccphylo_amd: tsv2phy failed: %s\n", emsg);
+			return 1;
+		}
+	}
+	free(X);
+	if(out) {
+		ccq_print_tsvphy(out, D, 8, m, (unsigned) flag, precision);
+		if(out != stdout) fclose(out);
+		else fflush(stdout);
+	}
+	if(treename) {
+		/* the names `tsv2phy | tree` would hold: the row indices as printed under -f */
+		char **names = malloc((size_t) m * sizeof(char *));
+		char *digits = malloc((size_t) m * 12);
+		for(int i = 0; i < m; ++i) {
+			names[i] = digits + (size_t) i * 12;
+			snprintf(names[i], 12, "%d", i);
+		}
+		ccq_names *T = ccq_names_new(32, 4);   /* as tree.c:61-66 */
+		ccq_names_set(T, names, m, (unsigned) flag, '\t');
+		fused_write_newick(tout, T, m, joins, nj, fn, fd, 0, precision);
+		fflush(stdout);
+		ccq_names_free(T);
+		free(names);
+		free(digits);
+	}
+	free(D);
+	free(joins);
+	return 0;
+}
+
 static int main_help(FILE *out) {
 	fprintf(out, "# CCPhylo (ccphylo_amd: MI355X engine for dist and tree)\n");
 	fprintf(out, "# Usage: ccphylo <command> [options]\n");
 	fprintf(out, "#    %-16s\t%s\n", "dist", "all-pairs SNP distances of an MSA (GPU)");
 	fprintf(out, "#    %-16s\t%s\n", "tree", "NJ / DNJ trees from Phylip matrices (GPU)");
 	fprintf(out, "#    %-16s\t%s\n", "dbscan", "DBSCAN clusters from Phylip matrices (GPU)");
+	fprintf(out, "#    %-16s\t%s\n", "tsv2phy", "all-pairs distances of a table's rows (GPU)");
 	return out == stderr;
 }
 
@@ -1169,7 +1429,8 @@ int main(int argc, char **argv) {
 	if(!strcmp(argv[1], "dist")) return main_dist(argc - 1, argv + 1);
 	if(!strcmp(argv[1], "tree")) return main_tree(argc - 1, argv + 1);
 	if(!strcmp(argv[1], "dbscan")) return main_dbscan(argc - 1, argv + 1);
+	if(!strcmp(argv[1], "tsv2phy")) return main_tsv2phy(argc - 1, argv + 1);
 	if(!strcmp(argv[1], "-h") || !strcmp(argv[1], "--help")) return main_help(stdout);
-	fprintf(stderr, "ccphylo_amd: command \"%s\" is outside the GPU engine's scope (dist, tree, dbscan).\n", argv[1]);
+	fprintf(stderr, "ccphylo_amd: command \"%s\" is outside the GPU engine's scope (dist, tree, dbscan, tsv2phy).\n", argv[1]);
 	return 1;
 }

@@ -91,6 +91,38 @@ class DbscanArgs(C.Structure):
                 ("minN", C.c_int)]
 
 
+class VecArgs(C.Structure):
+    _fields_ = [("m", C.c_int), ("n", C.c_int), ("stride", C.c_int64), ("vtype", C.c_int), ("X", C.c_void_p),
+                ("metric", C.c_int), ("exponent", C.c_double), ("etype", C.c_int)]
+
+
+# -d names of `ccphylo tsv2phy` (tsv2phy.c:316-357) -> CCG_VEC_*
+CCG_VEC_COS = 0
+CCG_VEC_CHI2 = 1
+CCG_VEC_BC = 2
+CCG_VEC_L1 = 3
+CCG_VEC_L2 = 4
+CCG_VEC_LINF = 5
+CCG_VEC_LN = 6
+CCG_VEC_PEARSON = 7
+VEC_METRICS = {"cos": CCG_VEC_COS, "chi2": CCG_VEC_CHI2, "bc": CCG_VEC_BC, "l1": CCG_VEC_L1, "l2": CCG_VEC_L2,
+               "linf": CCG_VEC_LINF, "p": CCG_VEC_PEARSON}
+
+
+def vec_metric(name):
+    """-d name -> (CCG_VEC_* id, exponent of l<n>); "l3" and "l2.5" are CCG_VEC_LN."""
+    if name in VEC_METRICS:
+        return VEC_METRICS[name], 0.0
+    if name.startswith("l") and len(name) > 1:
+        try:
+            ex = float(name[1:])
+        except ValueError:
+            ex = 0.0
+        if np.isfinite(ex) and ex > 0:
+            return CCG_VEC_LN, ex
+    raise ValueError(f"distance method {name!r} is not a tsv2phy method")
+
+
 class Join(C.Structure):
     _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("Li", C.c_double), ("Lj", C.c_double)]
 
@@ -125,6 +157,7 @@ ENGINE_SYMBOLS = [
     "ccg_kma_ltd", "ccg_kma_ltd_dev", "ccg_snp_ltd_shard_dev", "ccg_snp_ltd_shard", "ccg_selftest_row_sum",
     "ccg_round_decimal_dev", "ccg_last_dist_ms", "ccg_last_dist_plan", "ccg_tree_dev_state", "ccg_tree_shard_bytes", "ccg_ctx_configure",
     "ccg_shutdown", "ccg_dbscan", "ccg_dbscan_dev", "ccg_dbscan_count_dev",
+    "ccg_vec_ltd", "ccg_vec_ltd_dev", "ccg_last_vec_ms", "ccg_last_vec_plan",
 ]
 # every symbol of include/ccphylo_host.h
 HOST_SYMBOLS = [
@@ -134,7 +167,7 @@ HOST_SYMBOLS = [
     "ccq_replay_newick", "ccq_replay_newick_strings", "ccq_newick_pair",
     "ccq_code_table", "ccq_read_fasta", "ccq_pack", "ccq_init_inc", "ccq_inc_update", "ccq_npos",
     "ccq_load_msa", "ccq_load_msa_par", "ccq_msa_free", "ccq_load_fsa_files", "ccq_load_kma", "ccq_kma_free",
-    "ccq_print_dbscan",
+    "ccq_print_dbscan", "ccq_load_tsv", "ccq_print_tsvphy",
 ]
 
 _engine = None
@@ -208,6 +241,10 @@ def engine_lib():
                                    C.POINTER(C.c_int), C.POINTER(C.c_int64)]
         lib.ccg_dbscan_dev.argtypes = lib.ccg_dbscan.argtypes
         lib.ccg_dbscan_count_dev.argtypes = [C.c_void_p, C.POINTER(DbscanArgs), C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.ccg_vec_ltd.argtypes = [C.c_void_p, C.POINTER(VecArgs), C.c_void_p]
+        lib.ccg_vec_ltd_dev.argtypes = lib.ccg_vec_ltd.argtypes
+        lib.ccg_last_vec_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        lib.ccg_last_vec_plan.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         _engine = lib
     return _engine
 
@@ -251,6 +288,10 @@ def host_lib():
         lib.ccq_print_dbscan.restype = None
         lib.ccq_print_dbscan.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_int,
                                          C.c_int, C.c_double, C.c_int]
+        lib.ccq_load_tsv.argtypes = [C.c_void_p, C.c_char, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int),
+                                     C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
+        lib.ccq_print_tsvphy.restype = None
+        lib.ccq_print_tsvphy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint, C.c_int]
         _host = lib
     return _host
 
@@ -508,6 +549,45 @@ class Device:
                                              C.c_void_p(N_ptr) if N_ptr else None, C.byref(fatal)),
                     "ccg_kma_ltd_dev")
         return fatal.value
+
+    def vec_ltd(self, X, metric="cos", etype=8):
+        """`ccphylo tsv2phy`'s cells (ccg_vec_ltd): the packed LT of the
+        distances between the rows of X, a float64 (m, n) array, or a float32
+        one for the reference's `-p` storage.  metric: cos, chi2, bc, l1, l2,
+        linf, l<n> or p."""
+        X = np.asarray(X)
+        if X.dtype != np.float32:
+            X = np.asarray(X, dtype=np.float64)
+        assert X.ndim == 2
+        if X.strides[1] != X.itemsize or X.strides[0] % X.itemsize or X.strides[0] < X.shape[1] * X.itemsize:
+            X = np.ascontiguousarray(X)
+        m, n = X.shape
+        D = np.zeros(max(m * (m - 1) // 2, 1), dtype=ETYPES[etype])
+        a = self._vec_args(m, n, X.strides[0] // X.itemsize if m > 1 else n, X.itemsize, X.ctypes.data, metric, etype)
+        self._check(self.lib.ccg_vec_ltd(self.h, C.byref(a), D.ctypes.data), "ccg_vec_ltd")
+        return D[:m * (m - 1) // 2]
+
+    def vec_ltd_dev(self, X_ptr, m, n, D_ptr, stride=None, vtype=8, metric="cos", etype=8):
+        """ccg_vec_ltd_dev on a device table and a device LT buffer."""
+        a = self._vec_args(m, n, n if stride is None else stride, vtype, X_ptr, metric, etype)
+        self._check(self.lib.ccg_vec_ltd_dev(self.h, C.byref(a), C.c_void_p(D_ptr)), "ccg_vec_ltd_dev")
+
+    @staticmethod
+    def _vec_args(m, n, stride, vtype, ptr, metric, etype):
+        mid, ex = vec_metric(metric) if isinstance(metric, str) else (int(metric), 0.0)
+        return VecArgs(m, n, stride, vtype, ptr, mid, ex, etype)
+
+    def last_vec_ms(self):
+        """HIP-event duration of the last vec call's kernels (ccg_last_vec_ms)."""
+        ms = C.c_double(0)
+        self._check(self.lib.ccg_last_vec_ms(self.h, C.byref(ms)), "ccg_last_vec_ms")
+        return ms.value
+
+    def last_vec_plan(self):
+        """(tile edge, column chunk) of the last vec call's launch (ccg_last_vec_plan); (0, 0) when m < 2."""
+        t, k = C.c_int(0), C.c_int(0)
+        self._check(self.lib.ccg_last_vec_plan(self.h, C.byref(t), C.byref(k)), "ccg_last_vec_plan")
+        return t.value, k.value
 
     def last_dist_ms(self):
         """HIP-event duration of the last dist call's pair kernels (ccg_last_dist_ms)."""
@@ -876,6 +956,49 @@ def load_kma(files, tmpl, min_depth=15, min_length=1, min_cov=0.5, threads=16):
     finally:
         lib.ccq_kma_free(p)
     return out
+
+
+def load_tsv(path, sep="\t", vtype=8):
+    """A dense table as `ccphylo tsv2phy` reads it (ccq_load_tsv, ref tsv.c:30):
+    an ndarray (m, n) of float64, or float32 for vtype 4.  Raises ValueError
+    with the loader's message where the CLI would exit with status 1."""
+    lib = host_lib()
+    r = lib.ccq_open(path.encode())
+    if not r:
+        raise FileNotFoundError(path)
+    X = C.c_void_p()
+    m, n = C.c_int(0), C.c_int(0)
+    msg = C.create_string_buffer(256)
+    try:
+        rc = lib.ccq_load_tsv(r, sep.encode()[:1] or b"\t", vtype, C.byref(X), C.byref(m), C.byref(n), msg, 256)
+    finally:
+        lib.ccq_close(r)
+    if rc:
+        raise ValueError(msg.value.decode(errors="replace"))
+    dt = np.float64 if vtype == 8 else np.float32
+    if not m.value:
+        return np.zeros((0, n.value), dtype=dt)
+    try:
+        buf = (C.c_char * (m.value * n.value * vtype)).from_address(X.value)
+        return np.frombuffer(bytes(buf), dtype=dt).reshape(m.value, n.value).copy()
+    finally:
+        C.CDLL(None).free(X)
+
+
+def write_tsvphy(path, D, m, flag=1, precision=9, etype=8):
+    """Writes a packed LT as tsv2phy prints it (ccq_print_tsvphy, ref tsv2phy.c:64)."""
+    lib = host_lib()
+    libc = C.CDLL(None)
+    libc.fopen.restype = C.c_void_p
+    libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
+    libc.fclose.argtypes = [C.c_void_p]
+    D = np.ascontiguousarray(D, dtype=ETYPES[etype])
+    assert D.size == m * (m - 1) // 2
+    fp = libc.fopen(path.encode(), b"wb")
+    if not fp:
+        raise OSError(path)
+    lib.ccq_print_tsvphy(fp, D.ctypes.data if D.size else None, etype, m, flag, precision)
+    libc.fclose(fp)
 
 
 def write_phylip(path, D, n, names, flag=1, precision=9, etype=8, byte_scale=1.0):

@@ -22,6 +22,8 @@
  *   ccg_dbscan    replaces dbscan(D, N, C, maxDist, minN) (dbscan.c:31, called
  *                 dbscan.c:217); print_dbscan (dbscan.c:165) is
  *                 ccq_print_dbscan of include/ccphylo_host.h.
+ *   ccg_vec_ltd   replaces the distcmp_d / distcmp_f cell loop of tsv2phy
+ *                 (tsv2phy.c:86 / :92); loadTsv (tsv.c:30) is ccq_load_tsv.
  *   ccg_tree      replaces dnj_thread(D, sD, Q, N, names, t) (dnj.c:1054,
  *                 called tree.c:89) and nj_thread(D, sD, N, names, t)
  *                 (nj.c:1612, called tree.c:91).  It returns the join list;
@@ -418,6 +420,55 @@ int ccg_dbscan_dev(ccg_ctx *ctx, const ccg_dbscan_args *a, const void *D_dev, in
  * count and fany_dev[i] the smallest j < i with d(i,j) <= maxDist
  * (0x7f7f7f7f where there is none). */
 int ccg_dbscan_count_dev(ccg_ctx *ctx, const ccg_dbscan_args *a, const void *D_dev, int32_t *N_dev, int32_t *fany_dev);
+
+/* ------------------------------------------------------------------ */
+/* vec: all-pairs distances between the rows of a dense table          */
+/* ------------------------------------------------------------------ */
+/* Replaces the cell loop of tsv2phy (tsv2phy.c:86 / :92): distcmp_d(Di, Dj, n)
+ * (vtype 8) or distcmp_f (vtype 4, `-p`) for every pair j < i of the m rows,
+ * into the packed LT (row i holds (i,0) .. (i,i-1)).  Every cell is the
+ * reference's serial chain over the columns 0 .. n-1, operation by operation
+ * (separately rounded products and sums, float operands rounded to float
+ * first), so finite results equal the reference bit for bit; l<n> goes through
+ * pow() and agrees to a few ulp.  Non-finite results (a NaN's sign, sums that
+ * overflow) are not pinned. */
+#define CCG_VEC_COS     0   /* distcmp.c:414  1 - x.y / sqrt(x.x y.y), -1 at a zero norm, < 0 -> 0 */
+#define CCG_VEC_CHI2    1   /* :358  sqrt(sum (x-y)^2 / (x+y)) over x != y */
+#define CCG_VEC_BC      2   /* :298  1 - 2 sum min(x,y) / sum (x+y), < 0 -> 0 */
+#define CCG_VEC_L1      3   /* :30 */
+#define CCG_VEC_L2      4   /* :86 */
+#define CCG_VEC_LINF    5   /* :226 */
+#define CCG_VEC_LN      6   /* :142  pow(sum pow(|x-y|, exponent), 1 / exponent) */
+#define CCG_VEC_PEARSON 7   /* :510  the signed correlation, 0 at a zero variance */
+
+typedef struct {
+	int m, n;              /* rows, columns (n >= 1) */
+	int64_t stride;        /* elements between two rows (>= n) */
+	int vtype;             /* 8: double rows, 4: float rows */
+	const void *X;         /* m x n, row-major */
+	int metric;            /* CCG_VEC_* */
+	double exponent;       /* CCG_VEC_LN: finite and > 0 */
+	int etype;             /* of the LT: 8, or 4 (the double result cast once at the store) */
+} ccg_vec_args;
+
+/* X and D in HOST memory; D holds m(m-1)/2 elements of etype bytes.  m < 2
+ * writes nothing.  CCG_EINVAL (with a message for ccg_strerror(CCG_EHIP)'s
+ * slot) for n < 1, a bad vtype / metric / exponent / stride; CCG_EUNSUP for
+ * etype 2 / 1. */
+int ccg_vec_ltd(ccg_ctx *ctx, const ccg_vec_args *a, void *D);
+/* The same on DEVICE pointers (a->X and D_dev), with ccg_tree_dev's
+ * conventions: waits for the device first and for its own kernels at the end
+ * unless CCG_CTX_NOSYNC, runs on the context's stream.  D_dev is the LT that
+ * ccg_tree_dev and ccg_dbscan_dev take. */
+int ccg_vec_ltd_dev(ccg_ctx *ctx, const ccg_vec_args *a, void *D_dev);
+/* Milliseconds of the last vec call's pre-pass and pair kernel on this
+ * context (HIP events on the engine stream, as ccg_last_dist_ms); waits for
+ * them where a CCG_CTX_NOSYNC call has not.  0 when nothing ran (m < 2). */
+int ccg_last_vec_ms(ccg_ctx *ctx, double *ms);
+/* The launch form of the last vec call: *tile pairs per block side (64, or 32
+ * for tables of up to 3072 rows so that every CU gets tiles; the CCG_VEC_TILE knob forces
+ * one) and *chunk columns per LDS chunk.  0, 0 when nothing ran. */
+int ccg_last_vec_plan(ccg_ctx *ctx, int *tile, int *chunk);
 
 /* ------------------------------------------------------------------ */
 /* device memory helpers (for callers that keep the pipeline in HBM)   */

@@ -89,6 +89,21 @@ void ccq_print_phy(FILE *out, const ccq_ltd *D, char **names, const unsigned cha
 void ccq_print_dbscan(FILE *out, const char *header, char **names, const int32_t *N, const int32_t *C, int n,
                       int nclust, double maxDist, int minN);
 
+/* ---- dense tables (tsv2phy) ---- */
+/* tsv.c:30 loadTsv: drops the header line and the '#' lines after it, takes
+ * the column count from the last dropped line, then reads every line as one
+ * row of strtod numbers separated by `sep`.  On success returns 0 with *X a
+ * malloc'ed m x n row-major array of double (vtype 8) or float (vtype 4, each
+ * number rounded from its double as `-p` stores it); *m = 0 and *X = NULL for
+ * an input without rows.  Otherwise returns the exit status the CLI ends with
+ * (1) and the reason in msg: the reference's "Malformatted entry at pos:" (an
+ * entry of 32 or more bytes, trailing bytes) and "Unexpected end of file" (no
+ * final newline), and -- unlike the reference -- a nan / inf entry. */
+int ccq_load_tsv(ccq_reader *r, char sep, int vtype, void **X, int *m, int *n, char *msg, size_t msglen);
+/* tsv2phy.c:64-108: the Phylip text of a packed LT (etype 8 / 4) whose names
+ * are the row indices 0 .. m-1; format bit 1 = relaxed names. */
+void ccq_print_tsvphy(FILE *out, const void *D, int etype, int m, unsigned format, int precision);
+
 /* ---- Newick replay (GPU join list -> tree string) ---- */
 typedef struct {
 	int32_t i, j;          /* rows joined (j < i) at the time of the join */
