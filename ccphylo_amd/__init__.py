@@ -11,5 +11,6 @@ from .native import (CCG_TREE_CF, CCG_TREE_DNJ, CCG_TREE_FF, CCG_TREE_HNJ, CCG_T
                      engine_lib, host_lib, load_msa, load_phylip, newick_from_phylip, write_dbscan)
 from .native import (CCG_VEC_BC, CCG_VEC_CHI2, CCG_VEC_COS, CCG_VEC_L1, CCG_VEC_L2, CCG_VEC_LINF, CCG_VEC_LN,  # noqa: F401
                      CCG_VEC_PEARSON, load_tsv, vec_metric, write_tsvphy)
+from .native import MOTIF_DTYPE, load_motifs, meth_clear_row  # noqa: F401
 
 __version__ = "0.1.0"

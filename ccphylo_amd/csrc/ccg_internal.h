@@ -42,11 +42,11 @@ struct ccg_ctx {
 	// device workspaces kept across runs (grown on demand, freed by
 	// ccg_destroy): slots 0 / 1 the tree's, slot 2 the dist's bit planes in a
 	// CCG_CTX_NOSYNC context, slot 3 dbscan's per-row vectors, slot 4 the vec
-	// pre-pass's per-row values.  A run then
+	// pre-pass's per-row values, slot 5 the motif masking's counters.  A run then
 	// makes no hipFree, which waits for
 	// every stream of the device, so such a context never waits for another
-	void *ws[5];
-	size_t ws_bytes[5];
+	void *ws[6];
+	size_t ws_bytes[6];
 };
 // slot k of the context's workspace cache, at least `bytes` long
 int ccg_ctx_workspace(ccg_ctx *c, int k, size_t bytes, void **p);

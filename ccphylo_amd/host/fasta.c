@@ -152,6 +152,11 @@ int ccq_npos(const uint32_t *inc, int len) {
 
 ccq_msa *ccq_load_msa(ccq_reader *r, unsigned flag, unsigned minLength, double minCov,
                       unsigned proxi, FILE *log) {
+	return ccq_load_msa_meth(r, flag, minLength, minCov, proxi, NULL, 0, log);
+}
+
+ccq_msa *ccq_load_msa_meth(ccq_reader *r, unsigned flag, unsigned minLength, double minCov, unsigned proxi,
+                           const ccq_motif *motifs, int nmotifs, FILE *log) {
 	unsigned char table[256];
 	int variant = (flag & 32) ? 32 : (flag & 8) ? 8 : 0;
 	ccq_code_table(flag, table);
@@ -193,6 +198,12 @@ ccq_msa *ccq_load_msa(ccq_reader *r, unsigned flag, unsigned minLength, double m
 				ccq_inc_update(m, seq->seq, seq->seq, len, proxi, variant);
 				inc = ccq_npos(m, len);
 				keep = (unsigned) inc >= minLength;
+				if(nmotifs) {   /* the line waits for the count after masking (cdist.c:254-259) */
+					if(!keep) inc = ccq_meth_masked_npos(dst, m, len, motifs, nmotifs);
+					ccq_msa_pend_push(M, strdup(name), inc, keep ? M->n : -1);
+					if(keep) M->headers[M->n++] = strdup(name);
+					continue;
+				}
 			} else {
 				memset(dst, 0, W * sizeof(uint64_t));
 				inc = len - ccq_pack(seq->seq, len, dst);
@@ -227,6 +238,12 @@ ccq_msa *ccq_load_msa(ccq_reader *r, unsigned flag, unsigned minLength, double m
 			memset(dst, 0, W * sizeof(uint64_t));
 			ccq_pack(seq->seq, len, dst);
 			ccq_inc_update(m, seq->seq, seq->seq, len, proxi, variant);
+			if(nmotifs) {   /* cdist.c:302: the candidate's own sites, before its test */
+				uint32_t *clr = ccq_xmalloc((size_t) W * sizeof(uint32_t));
+				ccq_meth_clear_row(dst, len, motifs, nmotifs, clr);
+				for(int k = 0; k < W; ++k) m[k] &= ~clr[k];
+				free(clr);
+			}
 			int inc = ccq_npos(m, len);
 			if((unsigned) inc < minLength) {
 				fprintf(log, "# Excluded:\t%s\t( %d / %d )\n", name, inc, len);
@@ -257,6 +274,10 @@ void ccq_msa_free(ccq_msa *M) {
 		for(int i = 0; i < M->n; ++i) {
 			free(M->headers[i]);
 		}
+		for(int e = 0; e < M->npend; ++e) {
+			free(M->pend[e].name);
+		}
+		free(M->pend);
 		free(M->headers);
 		free(M->seqs);
 		free(M->incs);

@@ -303,6 +303,11 @@ static int locate(const unsigned char *buf, size_t blen, int eof, frec **recs, i
 
 ccq_msa *ccq_load_msa_par(ccq_reader *r, unsigned flag, unsigned minLength, double minCov, unsigned proxi, int threads,
                           FILE *log) {
+	return ccq_load_msa_par_meth(r, flag, minLength, minCov, proxi, threads, NULL, 0, log);
+}
+
+ccq_msa *ccq_load_msa_par_meth(ccq_reader *r, unsigned flag, unsigned minLength, double minCov, unsigned proxi,
+                               int threads, const ccq_motif *motifs, int nmotifs, FILE *log) {
 	unsigned char table[256];
 	const int variant = (flag & 32) ? 32 : (flag & 8) ? 8 : 0;
 	ccq_code_table(flag, table);
@@ -408,6 +413,12 @@ ccq_msa *ccq_load_msa_par(ccq_reader *r, unsigned flag, unsigned minLength, doub
 			memset(dst, 0, W * sizeof(uint64_t));
 			ccq_pack(scodes, len, dst);
 			ccq_inc_update(m, scodes, scodes, len, proxi, variant);
+			if(nmotifs) {   /* cdist.c:302: the candidate's own sites, before its test */
+				uint32_t *clr = ccq_xmalloc((size_t) W * sizeof(uint32_t));
+				ccq_meth_clear_row(dst, len, motifs, nmotifs, clr);
+				for(int k = 0; k < W; ++k) m[k] &= ~clr[k];
+				free(clr);
+			}
 			const int inc = ccq_npos(m, len);
 			if((unsigned) inc < minLength) {
 				fprintf(log, "# Excluded:\t%s\t( %d / %d )\n", f->name, inc, len);
@@ -472,8 +483,16 @@ ccq_msa *ccq_load_msa_par(ccq_reader *r, unsigned flag, unsigned minLength, doub
 					fprintf(stderr, "Sequences does not match: >%s\n", f->name);
 					exit(1);
 				}
-				fprintf(log, f->keep ? "# Included:\t%s\t( %d / %d )\n" : "# Excluded:\t%s\t( %d / %d )\n", f->name, f->inc,
-				        len);
+				if(M->pair && nmotifs) {
+					/* the line waits for the count after masking (cdist.c:254-259);
+					 * a record that fails already is counted here, in its provisional row */
+					const size_t at = (size_t) (w.slot0 + e) * W;
+					if(!f->keep) f->inc = ccq_meth_masked_npos(M->seqs + at, M->incs + at, len, motifs, nmotifs);
+					ccq_msa_pend_push(M, strdup(f->name), f->inc, f->keep ? M->n : -1);
+				} else {
+					fprintf(log, f->keep ? "# Included:\t%s\t( %d / %d )\n" : "# Excluded:\t%s\t( %d / %d )\n", f->name,
+					        f->inc, len);
+				}
 				if(!f->keep) {
 					free(f->name);
 					continue;

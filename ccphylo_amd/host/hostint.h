@@ -35,4 +35,10 @@ static inline int32_t ccq_cvt_i32(double x) {
 	return (int32_t) x;
 }
 
+/* motif.c: a record of a pair-mode motif load (the list owns name), and
+ * getNpos of a mask with the row's motif sites cleared */
+#include "ccphylo_host.h"
+void ccq_msa_pend_push(ccq_msa *M, char *name, int inc, int row);
+int ccq_meth_masked_npos(const uint64_t *seq, const uint32_t *inc, int len, const ccq_motif *motifs, int n);
+
 #endif

@@ -486,6 +486,7 @@ static int dist_help(FILE *out) {
 	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'o', "output", "Output file", "stdout");
 	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'n', "nucleotide_numbers", "Output number of nucleotides included", "False/None");
 	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'x', "print_precision", "Floating point print precision", "9");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'y', "methylation_motifs", "Mask methylation motifs from <file>", "False/None");
 	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'L', "min_len", "Minimum overlapping length", "1");
 	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'C', "min_cov", "Minimum coverage", "50.0%");
 	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'W', "normalization_weight", "Normalization weight", "0 / None");
@@ -761,6 +762,49 @@ static int dist_fsa_files(char **files, int nfiles, const char *tmpl, const char
 	return 0;
 }
 
+/* `dist -y FILE` (dist.c:127-132): the motif file, or exit(1) with the reason */
+static int load_motifs_or_die(const char *path, ccq_motif **mo) {
+	int n = 0;
+	char err[512];
+	if(ccq_load_motifs(path, mo, &n, err, sizeof(err))) {
+		fprintf(stderr, "ccphylo_amd: -y: %s.\n", err);
+		exit(1);
+	}
+	return n;
+}
+
+/* After a motif load: every included taxon's sites leave the include mask(s)
+ * on the GPU (maskMotifs at cdist.c:254 / :272, ccg_meth_mask), then a
+ * pair-mode load drops the records that fall below minLength and prints the
+ * held-back lines.  The packed rows go up once more for the distances. */
+static int apply_motifs(ccq_msa *M, const ccq_motif *mo, int nmo, int device) {
+	if(!nmo) return 0;
+	int32_t *cnt = NULL;
+	if(M->n > 0) {
+		ccg_ctx *ctx = open_gpu(device);
+		ccg_meth_args ma;
+		memset(&ma, 0, sizeof(ma));
+		ma.n = M->n;
+		ma.len = M->len;
+		ma.stride = M->W;
+		ma.seqs = M->seqs;
+		ma.incs = M->incs;
+		ma.pair = M->pair;
+		ma.motifs = (const ccg_motif *) mo;
+		ma.nmotifs = nmo;
+		cnt = malloc((size_t) M->n * sizeof(int32_t));
+		const int rc = ccg_meth_mask(ctx, &ma, cnt, NULL);
+		ccg_destroy(ctx);
+		if(rc) {
+			fprintf(stderr, "ccphylo_amd: methylation motif masking failed: %s\n", ccg_strerror(rc));
+			return 1;
+		}
+	}
+	ccq_msa_meth_finish(M, cnt, stderr);
+	free(cnt);
+	return 0;
+}
+
 /* `dist --tree FILE`: the MSA's distances and the tree in HBM, without the
  * Phylip text (configs[4]: a 1e6-taxon matrix has no text form).  With
  * --gpus G > 1 the LT is written straight into the ranks' row bands
@@ -773,7 +817,7 @@ static int dist_fsa_files(char **files, int nfiles, const char *tmpl, const char
 static int dist_tree(const char *in, const char *treename, const char *tmethod, int tflag, unsigned flag,
                      unsigned norm, unsigned minLength, double minCov, unsigned proxi, int precision, int et,
                      double bs, unsigned threads, int device, int gpus, int transport, int fast,
-                     const char *dbname, double maxDist, int minN) {
+                     const char *dbname, double maxDist, int minN, const char *methname) {
 	const int m = fused_tree_method(tmethod);
 	if(m < 0) return 1;
 	if(gpus > 1 && (m == CCG_TREE_CF || m == CCG_TREE_FF || m == CCG_TREE_MN)) {
@@ -810,8 +854,13 @@ static int dist_tree(const char *in, const char *treename, const char *tmethod, 
 		fprintf(stderr, "ccphylo_amd: --tree / --dbscan need an MSA (FASTA) input.\n");
 		return 1;
 	}
-	ccq_msa *M = ccq_load_msa_par(r, flag, minLength, minCov, proxi, threads > 16 ? (int) threads : 16, stderr);
+	ccq_motif *mo = NULL;
+	const int nmo = methname ? load_motifs_or_die(methname, &mo) : 0;
+	ccq_msa *M = ccq_load_msa_par_meth(r, flag, minLength, minCov, proxi, threads > 16 ? (int) threads : 16, mo, nmo,
+	                                   stderr);
 	ccq_close(r);
+	if(apply_motifs(M, mo, nmo, device)) return 1;
+	free(mo);
 	const int n = M->n;
 	if(treename && n < 3) {
 		fprintf(stderr, "ccphylo_amd: --tree needs at least 3 included sequences (%d).\n", n);
@@ -907,7 +956,7 @@ static int main_dist(int argc, char **argv) {
 	int nfiles = 0, precision = 9, et = 8, device = 0, gpus = 0, transport = CCQ_TRANSPORT_RCCL, fast = 0, tflag = 0;
 	unsigned flag = 1, norm = 0, minLength = 1, proxi = 0, minDepth = 15, threads = 1;
 	double minCov = 0.5, bs = 1.0;
-	const char *unsup = NULL, *tmpl = NULL, *method = "cos";
+	const char *unsup = NULL, *tmpl = NULL, *method = "cos", *methname = NULL;
 	Args A = {argc, 0, argv};
 	for(A.k = 1; A.k < argc; ++A.k) {
 		char *a = argv[A.k];
@@ -968,8 +1017,8 @@ static int main_dist(int argc, char **argv) {
 			else if(!strcmp(name, "min_depth")) minDepth = (unsigned) strtod(opt_value(&A, att, name), NULL);
 			else if(!strcmp(name, "significance_lvl")) (void) opt_value(&A, att, name);
 			else if(!strcmp(name, "reference")) tmpl = opt_value(&A, att, name);
-			else if(!strcmp(name, "add") || !strcmp(name, "methylation_motifs") ||
-			        !strcmp(name, "nucleotide_variations")) { (void) opt_value(&A, att, name); unsup = name; }
+			else if(!strcmp(name, "methylation_motifs")) methname = opt_value(&A, att, name);
+			else if(!strcmp(name, "add") || !strcmp(name, "nucleotide_variations")) { (void) opt_value(&A, att, name); unsup = name; }
 			else if(!strcmp(name, "help")) return dist_help(stdout);
 			else die_opt("Unknown", a);
 			continue;
@@ -1007,7 +1056,8 @@ static int main_dist(int argc, char **argv) {
 				case 'E': minDepth = (unsigned) strtod(opt_value(&A, att, "E"), NULL); break;
 				case 'l': (void) opt_value(&A, att, "l"); break;
 				case 'r': tmpl = opt_value(&A, att, "r"); break;
-				case 'a': case 'y': case 'V': {
+				case 'y': methname = opt_value(&A, att, "y"); break;
+				case 'a': case 'V': {
 					static char nm[2];
 					nm[0] = o;
 					(void) opt_value(&A, att, nm);
@@ -1068,7 +1118,11 @@ static int main_dist(int argc, char **argv) {
 		fprintf(stderr, "ccphylo_amd: dist option \"%s\" is not implemented by the GPU engine.\n", unsup);
 		return 1;
 	}
-	if(tmpl && nfiles > 1 && !(flag & 16) && first_byte(files[0]) != '>') {   /* dist.c:99-108 */
+	if(methname && nfiles > 1 && !(tmpl && !(flag & 16) && first_byte(files[0]) != '>')) {
+		fprintf(stderr, "ccphylo_amd: -y with several FASTA files (-r) is not implemented by the GPU engine: use one MSA.\n");
+		return 1;
+	}
+	if(tmpl && nfiles > 1 && !(flag & 16) && first_byte(files[0]) != '>') {   /* dist.c:99-108: .mat input ignores -y */
 		return dist_kma(files, nfiles, tmpl, outname, noutname, metric, lnorm, norm, minDepth, minLength, minCov,
 		                flag, precision, et, bs, threads, device);
 	}
@@ -1082,7 +1136,7 @@ static int main_dist(int argc, char **argv) {
 	}
 	if(treename || dbname) {
 		return dist_tree(nfiles ? files[0] : "-", treename, tmethod, tflag, flag, norm, minLength, minCov, proxi,
-		                 precision, et, bs, threads, device, gpus, transport, fast, dbname, maxDist, minN);
+		                 precision, et, bs, threads, device, gpus, transport, fast, dbname, maxDist, minN, methname);
 	}
 	FILE *out = (outname[0] == '-' && outname[1] == 0) ? stdout : fopen(outname, "wb");
 	if(!out) {
@@ -1108,8 +1162,13 @@ static int main_dist(int argc, char **argv) {
 	}
 	/* the per-sequence work on host threads (fasta_par.c; the same result as
 	 * the serial ccq_load_msa) */
-	ccq_msa *M = ccq_load_msa_par(r, flag, minLength, minCov, proxi, threads > 16 ? (int) threads : 16, stderr);
+	ccq_motif *mo = NULL;
+	const int nmo = methname ? load_motifs_or_die(methname, &mo) : 0;
+	ccq_msa *M = ccq_load_msa_par_meth(r, flag, minLength, minCov, proxi, threads > 16 ? (int) threads : 16, mo, nmo,
+	                                   stderr);
 	ccq_close(r);
+	if(apply_motifs(M, mo, nmo, device)) return 1;
+	free(mo);
 	int n = M->n;
 	if(n * (n - 1) / 2 < 1) {
 		fprintf(stderr, "Adjustning number of nodes to %d, to conform with the matrix size.\n", n * (n - 1) / 2);

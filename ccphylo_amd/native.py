@@ -123,6 +123,16 @@ def vec_metric(name):
     raise ValueError(f"distance method {name!r} is not a tsv2phy method")
 
 
+# one strand of a methylation motif (ccg_motif / ccq_motif): allow[k] = 1 A, 2 C, 4 G, 8 T ored;
+# meth bit 31 - k = base k is a site
+MOTIF_DTYPE = np.dtype([("len", np.int32), ("meth", np.uint32), ("allow", np.uint8, (32,))])
+
+
+class MethArgs(C.Structure):
+    _fields_ = [("n", C.c_int), ("len", C.c_int), ("stride", C.c_int), ("seqs", C.c_void_p), ("incs", C.c_void_p),
+                ("pair", C.c_int), ("motifs", C.c_void_p), ("nmotifs", C.c_int)]
+
+
 class Join(C.Structure):
     _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("Li", C.c_double), ("Lj", C.c_double)]
 
@@ -158,6 +168,7 @@ ENGINE_SYMBOLS = [
     "ccg_round_decimal_dev", "ccg_last_dist_ms", "ccg_last_dist_plan", "ccg_tree_dev_state", "ccg_tree_shard_bytes", "ccg_ctx_configure",
     "ccg_shutdown", "ccg_dbscan", "ccg_dbscan_dev", "ccg_dbscan_count_dev",
     "ccg_vec_ltd", "ccg_vec_ltd_dev", "ccg_last_vec_ms", "ccg_last_vec_plan",
+    "ccg_meth_mask", "ccg_meth_mask_dev",
 ]
 # every symbol of include/ccphylo_host.h
 HOST_SYMBOLS = [
@@ -168,6 +179,7 @@ HOST_SYMBOLS = [
     "ccq_code_table", "ccq_read_fasta", "ccq_pack", "ccq_init_inc", "ccq_inc_update", "ccq_npos",
     "ccq_load_msa", "ccq_load_msa_par", "ccq_msa_free", "ccq_load_fsa_files", "ccq_load_kma", "ccq_kma_free",
     "ccq_print_dbscan", "ccq_load_tsv", "ccq_print_tsvphy",
+    "ccq_load_motifs", "ccq_meth_clear_row", "ccq_load_msa_meth", "ccq_load_msa_par_meth", "ccq_msa_meth_finish",
 ]
 
 _engine = None
@@ -245,6 +257,8 @@ def engine_lib():
         lib.ccg_vec_ltd_dev.argtypes = lib.ccg_vec_ltd.argtypes
         lib.ccg_last_vec_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         lib.ccg_last_vec_plan.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.ccg_meth_mask.argtypes = [C.c_void_p, C.POINTER(MethArgs), C.c_void_p, C.POINTER(C.c_int64)]
+        lib.ccg_meth_mask_dev.argtypes = lib.ccg_meth_mask.argtypes
         _engine = lib
     return _engine
 
@@ -281,6 +295,17 @@ def host_lib():
         lib.ccq_load_msa_par.restype = C.c_void_p
         lib.ccq_load_msa_par.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_double, C.c_uint, C.c_int, C.c_void_p]
         lib.ccq_msa_free.argtypes = [C.c_void_p]
+        lib.ccq_load_motifs.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
+        lib.ccq_meth_clear_row.restype = C.c_int64
+        lib.ccq_meth_clear_row.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        lib.ccq_load_msa_meth.restype = C.c_void_p
+        lib.ccq_load_msa_meth.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_double, C.c_uint, C.c_void_p, C.c_int,
+                                          C.c_void_p]
+        lib.ccq_load_msa_par_meth.restype = C.c_void_p
+        lib.ccq_load_msa_par_meth.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_double, C.c_uint, C.c_int, C.c_void_p,
+                                              C.c_int, C.c_void_p]
+        lib.ccq_msa_meth_finish.restype = None
+        lib.ccq_msa_meth_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.ccq_load_kma.restype = C.c_void_p
         lib.ccq_load_kma.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_uint, C.c_uint, C.c_double, C.c_int,
                                      C.c_void_p]
@@ -312,7 +337,7 @@ class _Names(C.Structure):
 class _Msa(C.Structure):
     _fields_ = [("n", C.c_int), ("len", C.c_int), ("W", C.c_int), ("pair", C.c_int),
                 ("headers", C.POINTER(C.c_char_p)), ("seqs", C.POINTER(C.c_uint64)),
-                ("incs", C.POINTER(C.c_uint32)), ("minLength", C.c_uint)]
+                ("incs", C.POINTER(C.c_uint32)), ("minLength", C.c_uint), ("npend", C.c_int), ("pend", C.c_void_p)]
 
 
 class _Kma(C.Structure):
@@ -631,6 +656,37 @@ class Device:
     def sync(self):
         self._check(self.lib.ccg_synchronize(self.h), "ccg_synchronize")
 
+    def meth_mask(self, seqs, incs, n, length, motifs, pair=False):
+        """`dist -y` on the GPU (ccg_meth_mask): the sites of every motif strand
+        (MOTIF_DTYPE, e.g. from load_motifs) in each of the n packed rows
+        seqs uint64[n, stride] leave the include mask(s) incs (uint32[stride],
+        or uint32[n, stride] with pair).  Returns (incs, inc_count int32[n],
+        matches): a masked copy, getNpos of each taxon's mask (pair) or of the
+        one mask in every slot, and the sites found."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint64)
+        incs = np.array(incs, dtype=np.uint32, order="C")
+        motifs = np.ascontiguousarray(motifs, dtype=MOTIF_DTYPE)
+        a = MethArgs(n, length, seqs.shape[1], seqs.ctypes.data, incs.ctypes.data, int(pair),
+                     motifs.ctypes.data, len(motifs))
+        cnt = np.zeros(max(n, 1), dtype=np.int32)
+        mt = C.c_int64(0)
+        self._check(self.lib.ccg_meth_mask(self.h, C.byref(a), cnt.ctypes.data, C.byref(mt)), "ccg_meth_mask")
+        return incs, cnt[:n], mt.value
+
+    def meth_mask_dev(self, seqs_ptr, incs_ptr, n, length, stride, motifs, pair=False, want_counts=True):
+        """ccg_meth_mask_dev: the same on device pointers, the mask(s) updated
+        in place.  Returns (inc_count, matches), or None without want_counts
+        (a nosync context then does not wait for the kernels)."""
+        motifs = np.ascontiguousarray(motifs, dtype=MOTIF_DTYPE)
+        a = MethArgs(n, length, stride, seqs_ptr, incs_ptr, int(pair), motifs.ctypes.data, len(motifs))
+        if not want_counts:
+            self._check(self.lib.ccg_meth_mask_dev(self.h, C.byref(a), None, None), "ccg_meth_mask_dev")
+            return None
+        cnt = np.zeros(max(n, 1), dtype=np.int32)
+        mt = C.c_int64(0)
+        self._check(self.lib.ccg_meth_mask_dev(self.h, C.byref(a), cnt.ctypes.data, C.byref(mt)), "ccg_meth_mask_dev")
+        return cnt[:n], mt.value
+
     def snp_ltd_dev(self, seqs_ptr, incs_ptr, n, length, stride, D_ptr, N_ptr=None, pair=False, norm=0,
                     min_length=1, etype=8, byte_scale=1.0, row_range=(0, 0)):
         """ccg_snp_ltd_dev on device pointers.  Returns getNpos(mask) (non-pair)."""
@@ -889,11 +945,46 @@ def newick_from_phylip(path, joins_fn, etype=8, byte_scale=1.0, flags=0, precisi
     return trees
 
 
-def load_msa(path, flag=1, min_length=1, min_cov=0.5, proxi=0, threads=0, log_path=None):
+def load_motifs(path):
+    """The methylation motif file of `dist -y` (ccq_load_motifs): a MOTIF_DTYPE
+    array with two strands per record, the motif as written and strrcMeth of
+    it.  Raises CcgError with the reason for a motif the engine refuses."""
+    lib = host_lib()
+    p, n = C.c_void_p(), C.c_int(0)
+    err = C.create_string_buffer(512)
+    if lib.ccq_load_motifs(os.fsencode(path), C.byref(p), C.byref(n), err, 512):
+        raise CcgError(err.value.decode())
+    out = np.zeros(n.value, dtype=MOTIF_DTYPE)
+    if n.value:
+        C.memmove(out.ctypes.data, p, out.nbytes)
+    C.CDLL(None).free(p)
+    return out
+
+
+def meth_clear_row(seq, length, motifs):
+    """ccq_meth_clear_row: (clear words uint32[length // 32 + 1], matches) of one packed row."""
+    seq = np.ascontiguousarray(seq, dtype=np.uint64)
+    motifs = np.ascontiguousarray(motifs, dtype=MOTIF_DTYPE)
+    clr = np.zeros(length // 32 + 1, dtype=np.uint32)
+    m = host_lib().ccq_meth_clear_row(seq.ctypes.data, length, motifs.ctypes.data, len(motifs), clr.ctypes.data)
+    return clr, m
+
+
+def load_msa(path, flag=1, min_length=1, min_cov=0.5, proxi=0, threads=0, log_path=None, motifs=None, dev=None,
+             mask_fn=None):
     """FASTA MSA -> (headers, seqs uint64[n, W], incs, minLength) per ltdMsaMatrix_get.
     threads > 0: the parallel loader (ccq_load_msa_par); log_path: where the
-    Included / Excluded lines go (default /dev/null)."""
+    Included / Excluded lines go (default /dev/null).
+    motifs (MOTIF_DTYPE, `dist -y`): the motif loaders; with dev (a Device)
+    the sites of every taxon are then cleared on the GPU (ccg_meth_mask) and a
+    pair-mode load is finished (ccq_msa_meth_finish), so the result is what
+    `dist -y` computes on.  Without dev only the reference record is masked and
+    a pair-mode load keeps its provisional rows.  mask_fn(seqs, incs, n,
+    length, pair) -> inc_count stands in for the GPU step (it clears incs, a
+    view of the loader's masks, in place): tests of the host layer."""
     lib = host_lib()
+    if motifs is not None:
+        motifs = np.ascontiguousarray(motifs, dtype=MOTIF_DTYPE)
     r = lib.ccq_open(path.encode())
     if not r:
         raise FileNotFoundError(path)
@@ -904,10 +995,28 @@ def load_msa(path, flag=1, min_length=1, min_cov=0.5, proxi=0, threads=0, log_pa
     log = libc.fopen((log_path or "/dev/null").encode(), b"w")
     try:
         lib.ccq_peek(r)
-        if threads > 0:
+        if motifs is not None and threads > 0:
+            Mp = lib.ccq_load_msa_par_meth(r, flag, min_length, min_cov, proxi, threads, motifs.ctypes.data,
+                                           len(motifs), log)
+        elif motifs is not None:
+            Mp = lib.ccq_load_msa_meth(r, flag, min_length, min_cov, proxi, motifs.ctypes.data, len(motifs), log)
+        elif threads > 0:
             Mp = lib.ccq_load_msa_par(r, flag, min_length, min_cov, proxi, threads, log)
         else:
             Mp = lib.ccq_load_msa(r, flag, min_length, min_cov, proxi, log)
+        if motifs is not None and len(motifs) and (dev is not None or mask_fn is not None):
+            M = _Msa.from_address(Mp)
+            cnt = np.zeros(max(M.n, 1), dtype=np.int32)
+            if M.n and mask_fn is not None:
+                sv = np.ctypeslib.as_array(M.seqs, shape=(M.n * M.W,)).reshape(M.n, M.W)
+                iv = np.ctypeslib.as_array(M.incs, shape=((M.n if M.pair else 1) * M.W,))
+                cnt = np.ascontiguousarray(mask_fn(sv, iv.reshape(M.n, M.W) if M.pair else iv, M.n, M.len, bool(M.pair)),
+                                           dtype=np.int32)
+            elif M.n:
+                a = MethArgs(M.n, M.len, M.W, C.cast(M.seqs, C.c_void_p), C.cast(M.incs, C.c_void_p), M.pair,
+                             motifs.ctypes.data, len(motifs))
+                dev._check(dev.lib.ccg_meth_mask(dev.h, C.byref(a), cnt.ctypes.data, None), "ccg_meth_mask")
+            lib.ccq_msa_meth_finish(Mp, cnt.ctypes.data, log)
     finally:
         lib.ccq_close(r)
         libc.fclose(log)

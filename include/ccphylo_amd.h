@@ -24,6 +24,10 @@
  *                 ccq_print_dbscan of include/ccphylo_host.h.
  *   ccg_vec_ltd   replaces the distcmp_d / distcmp_f cell loop of tsv2phy
  *                 (tsv2phy.c:86 / :92); loadTsv (tsv.c:30) is ccq_load_tsv.
+ *   ccg_meth_mask replaces the per-sequence maskMotifs calls of `dist -y`
+ *                 (meth.c:141, called cdist.c:254 / :272 / :302): one pass
+ *                 over the packed rows; getMethMotifs (methparse.c:254) is
+ *                 ccq_load_motifs of include/ccphylo_host.h.
  *   ccg_tree      replaces dnj_thread(D, sD, Q, N, names, t) (dnj.c:1054,
  *                 called tree.c:89) and nj_thread(D, sD, N, names, t)
  *                 (nj.c:1612, called tree.c:91).  It returns the join list;
@@ -469,6 +473,46 @@ int ccg_last_vec_ms(ccg_ctx *ctx, double *ms);
  * for tables of up to 3072 rows so that every CU gets tiles; the CCG_VEC_TILE knob forces
  * one) and *chunk columns per LDS chunk.  0, 0 when nothing ran. */
 int ccg_last_vec_plan(ccg_ctx *ctx, int *tile, int *chunk);
+
+/* ------------------------------------------------------------------ */
+/* meth: `dist -y` methylation motif sites out of the include masks    */
+/* ------------------------------------------------------------------ */
+/* Replaces maskMotifs(seq, include, len, motif) (meth.c:141, called
+ * cdist.c:254 / :272 / :302).  One ccg_motif per strand (the host parser
+ * ccq_load_motifs yields the motif as written, then strrcMeth of it): the
+ * strand matches at start p, 0 <= p <= len - m, when the packed code at
+ * p + k lies in allow[k] for every k (codes stored as 00 -- N, gaps -- are
+ * `A`; the zero padding behind len - 1 never completes a match; matches may
+ * overlap), and a match clears include bit 31 - (pos % 32) of word pos / 32
+ * for every site pos = p + k. */
+typedef struct {
+	int32_t len;           /* 2 .. 32 */
+	uint32_t meth;         /* bit 31 - k: base k is a methylation site */
+	uint8_t allow[32];     /* allow[k]: 1 A, 2 C, 4 G, 8 T, ored */
+} ccg_motif;
+
+typedef struct {
+	int n, len, stride;    /* as ccg_snp_args */
+	const uint64_t *seqs;  /* n * stride */
+	uint32_t *incs;        /* stride (pair = 0) or n * stride (pair = 1), updated in place */
+	int pair;              /* 0: every taxon clears into the one mask; 1: into its own */
+	const ccg_motif *motifs;   /* host memory in both forms */
+	int nmotifs;           /* any number; the engine batches its launches */
+} ccg_meth_args;
+
+/* Host buffers, the rows streamed through the staging buffer as ccg_snp_ltd's.
+ * inc_count (n entries, may be NULL): getNpos of taxon t's final mask (pair),
+ * or of the global mask in every slot.  *matches (may be NULL): the sites
+ * found over all taxa and strands, a palindrome counting on both strands as
+ * maskMotifs' return value does.  nmotifs = 0 or n = 0 does nothing.
+ * CCG_EINVAL for a strand length outside 2 .. 32, an empty allow[k] below its
+ * length, or meth bits at or beyond it. */
+int ccg_meth_mask(ccg_ctx *ctx, const ccg_meth_args *a, int32_t *inc_count, int64_t *matches);
+/* The same with a->seqs / a->incs DEVICE pointers (inc_count / matches stay
+ * host memory), with ccg_tree_dev's conventions: waits for the device first
+ * unless CCG_CTX_NOSYNC, runs on the context's stream, and returns after its
+ * kernels -- except in a CCG_CTX_NOSYNC context asked for neither output. */
+int ccg_meth_mask_dev(ccg_ctx *ctx, const ccg_meth_args *a, int32_t *inc_count, int64_t *matches);
 
 /* ------------------------------------------------------------------ */
 /* device memory helpers (for callers that keep the pipeline in HBM)   */

@@ -133,6 +133,23 @@ void ccq_init_inc(uint32_t *inc, int len);
 void ccq_inc_update(uint32_t *inc, unsigned char *seq, unsigned char *ref, int len, unsigned proxi, int variant);
 int ccq_npos(const uint32_t *inc, int len);
 
+/* One strand of a methylation motif (`dist -y`), the layout of ccg_motif
+ * (include/ccphylo_amd.h): allow[k] the 4-bit base set (A 1, C 2, G 4, T 8)
+ * of base k, meth bit 31 - k set where base k is a methylation site. */
+typedef struct {
+	int32_t len;
+	uint32_t meth;
+	uint8_t allow[32];
+} ccq_motif;
+
+/* A record after the reference of a pair-mode motif load, in record order.
+ * row >= 0: kept provisionally in that row, its line waiting for the count
+ * after motif masking; row = -1: excluded at once, inc its final count. */
+typedef struct ccq_pend {
+	char *name;
+	int inc, row;
+} ccq_pend;
+
 /* An MSA loaded per ltdMsaMatrix_get (cdist.c:196-333): included taxa only,
  * packed seqs (stride W = len/32 + 1 words) and mask(s). */
 typedef struct {
@@ -141,6 +158,8 @@ typedef struct {
 	uint64_t *seqs;        /* n * W */
 	uint32_t *incs;        /* W (non-pair) or n * W (pair) */
 	unsigned minLength;    /* after the minCov adjustment (cdist.c:289) */
+	int npend;             /* a pair-mode motif load: the records whose line is held back */
+	struct ccq_pend *pend;
 } ccq_msa;
 
 /* Reads every record; logs "# Included/# Excluded" to `log` like the
@@ -154,6 +173,40 @@ void ccq_msa_free(ccq_msa *M);
  * come in record order as the reference prints them. */
 ccq_msa *ccq_load_msa_par(ccq_reader *r, unsigned flag, unsigned minLength, double minCov, unsigned proxi, int threads,
                           FILE *log);
+
+/* ---- methylation motifs (`dist -y`) ---- */
+/* getMethMotifs (methparse.c:254): a FASTA file (gzip accepted) whose records'
+ * IUPAC letters give one base set each -- an uppercase letter also marks a
+ * methylation site -- every other byte dropped.  Each record yields two
+ * entries: the motif as written, then strrcMeth of it (methparse.c:84: for an
+ * odd length not the true reverse complement, reproduced as it is).  Returns 0
+ * with *motifs malloc'ed (2 per record), or 1 with the reason, naming the
+ * record, in err: an unreadable file, or a motif where the reference is
+ * undefined -- no base, one base, more than 32, or a site on a base whose set
+ * is narrower than the motif's widest set. */
+int ccq_load_motifs(const char *path, ccq_motif **motifs, int *n, char *err, size_t errlen);
+/* maskMotifs (meth.c:141) on one packed row, position by position: strand j
+ * matches at start p, 0 <= p <= len - m, when the 2-bit code at p + k is in
+ * allow[k] for all k (a code stored as 00 is `A`; matches may overlap).
+ * clear_words (len / 32 + 1 words, overwritten) gets bit 31 - (pos % 32) of
+ * word pos / 32 for every site of every match; returns the matches. */
+int64_t ccq_meth_clear_row(const uint64_t *seq, int len, const ccq_motif *motifs, int n, uint32_t *clear_words);
+/* ccq_load_msa / ccq_load_msa_par for `dist -y` (nmotifs = 0: exactly those).
+ * The record that becomes the reference is masked here before its inclusion
+ * test (cdist.c:302-305).  Non-pair mode is otherwise unchanged: the caller
+ * clears the sites of all taxa from M->incs with ccg_meth_mask.  Pair mode
+ * counts a record after masking (cdist.c:254-259): a record that fails before
+ * masking is excluded at once, the others are kept provisionally and every
+ * line after the reference's is held back in M->pend for ccq_msa_meth_finish. */
+ccq_msa *ccq_load_msa_meth(ccq_reader *r, unsigned flag, unsigned minLength, double minCov, unsigned proxi,
+                           const ccq_motif *motifs, int nmotifs, FILE *log);
+ccq_msa *ccq_load_msa_par_meth(ccq_reader *r, unsigned flag, unsigned minLength, double minCov, unsigned proxi,
+                               int threads, const ccq_motif *motifs, int nmotifs, FILE *log);
+/* After ccg_meth_mask on a pair-mode motif load: inc_count[row] decides the
+ * provisional rows (kept when >= M->minLength), the held-back lines go to
+ * `log` in record order with the reference's bytes, and the rows are
+ * compacted (M->n shrinks).  Does nothing for any other load. */
+void ccq_msa_meth_finish(ccq_msa *M, const int32_t *inc_count, FILE *log);
 
 /* Multi-file FASTA with -r (cdist.c:36 ltdFsaMatrix_get): entry `tmpl` of
  * every file; n = nfiles (every file keeps its slot), include[nfiles] the
