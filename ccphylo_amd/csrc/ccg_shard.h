@@ -5,7 +5,7 @@
 #pragma once
 #include <stdio.h>
 #include <string.h>
-#include "ccg_tree_common.h"
+#include "ccg_tree_run.h"
 
 #include "ccg_shard_layout.h"
 static_assert(SB == NJ_RB, "a shard band is one NJ argmin row band");

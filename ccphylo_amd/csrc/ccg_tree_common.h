@@ -1393,56 +1393,3 @@ __device__ __forceinline__ void qf_wave_reduce(double &q, long long &f) {
 	q = readlane_d(q, 63);
 	f = readlane_l(f, 63);
 }
-
-
-// ------------------------------------------------------------------ host
-// Per-kernel HIP-event timing (profile mode): one event after every launch,
-// harvested in batches.
-struct KTimer {
-	bool on;
-	hipStream_t st;
-	hipEvent_t ev[1025];
-	int cls[1025];
-	int used;
-	long long cnt[CCG_NKSTAT], ns[CCG_NKSTAT];
-	void init(hipStream_t s, bool enable) {
-		if(on)   // a previous profiled run that ended early (an error return) still holds its events
-			for(int k = 0; k < 1025; ++k) hipEventDestroy(ev[k]);
-		on = enable;
-		st = s;
-		used = 0;
-		memset(cnt, 0, sizeof(cnt));
-		memset(ns, 0, sizeof(ns));
-		if(on) {
-			for(int k = 0; k < 1025; ++k) hipEventCreate(&ev[k]);
-			hipEventRecord(ev[0], st);
-			used = 1;
-		}
-	}
-	void harvest() {
-		hipEventSynchronize(ev[used - 1]);
-		for(int k = 1; k < used; ++k) {
-			float ms = 0;
-			hipEventElapsedTime(&ms, ev[k - 1], ev[k]);
-			cnt[cls[k]] += 1;
-			ns[cls[k]] += (long long) (ms * 1.0e6);
-		}
-		hipEvent_t t = ev[0];
-		ev[0] = ev[used - 1];
-		ev[used - 1] = t;
-		used = 1;
-	}
-	void mark(int c) {
-		if(!on) return;
-		cls[used] = c;
-		hipEventRecord(ev[used++], st);
-		if(used == 1025) harvest();
-	}
-	void finish() {
-		if(!on) return;
-		harvest();
-		for(int k = 0; k < 1025; ++k) hipEventDestroy(ev[k]);
-		on = false;   // later marks (e.g. a final collective) are not timed
-	}
-};
-

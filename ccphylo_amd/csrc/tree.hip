@@ -43,7 +43,7 @@
 #include <stdio.h>
 #include <vector>
 #include <stdlib.h>
-#include "ccg_tree_common.h"
+#include "ccg_tree_run.h"
 
 #include "ccg_dnj_search.h"
 
@@ -1851,7 +1851,6 @@ static int enqueue_iteration(hipStream_t st, typename Elem<ET>::T *D, double bs,
                              int method, int exact, KTimer &kt) {
 	const unsigned gn = cdiv(n, TB);
 	const int general = GEN;
-	const int xs = 0;   // exact row sums: split over the join kernel and its consumer (xs_join_row, xs_walk_blocks)
 	if(method == CCG_TREE_DNJ) {
 		const int seg = g_grid.seg(n), prefold = g_grid.prefold(n);
 		const ScanForm f = dnj_scan_form(g_grid, n, ET, GEN, b.lbm != NULL);
@@ -1871,17 +1870,13 @@ static int enqueue_iteration(hipStream_t st, typename Elem<ET>::T *D, double bs,
 		else k_dnj_join<ET, GEN><<<gn, TB, 0, st>>>(D, bs, b, n, general, prefold, seg);
 		if(GEN) k_update_general<ET><<<1, 1024, 0, st>>>(D, bs, b, n);
 		kt.mark(CCG_K_UPDATE);
-		if(xs) {
-			k_exact_sum<><<<1, XS_NT, 0, st>>>(b, n, (int) gn);
-			kt.mark(CCG_K_XSUM);
-		}
 		// the requeue leaves the V block minima for the next join's pruning
 		if(g_grid.bands(n - 1) && g_grid.scan_vblk && dnj_scan_form(g_grid, n - 1, ET, GEN, b.lbm != NULL).prune)
 			k_dnj_requeue<ET, true, true><<<gn, TB, 0, st>>>(D, bs, b, n, general, exact);
 		else if(g_grid.bands(n - 1)) k_dnj_requeue<ET, true><<<gn, TB, 0, st>>>(D, bs, b, n, general, exact);
 		else k_dnj_requeue<ET, false><<<gn, TB, 0, st>>>(D, bs, b, n, general, exact);
 		kt.mark(CCG_K_REQUEUE);
-		return (GEN ? 4 : 3) + f.launches + xs;   // plan, join (+ update), requeue; the scan leg
+		return (GEN ? 4 : 3) + f.launches;   // plan, join (+ update), requeue; the scan leg
 	}
 	if(method == CCG_TREE_HNJ) {
 		k_hnj_argmin<><<<gn, TB, 0, st>>>(b, n);
@@ -1889,13 +1884,9 @@ static int enqueue_iteration(hipStream_t st, typename Elem<ET>::T *D, double bs,
 		k_nj_join<ET><<<gn, TB, 0, st>>>(D, bs, b, n, (int) gn, general, DBL_MAX);
 		if(GEN) k_update_general<ET><<<1, 1024, 0, st>>>(D, bs, b, n);
 		kt.mark(CCG_K_UPDATE);
-		if(xs) {
-			k_exact_sum<><<<1, XS_NT, 0, st>>>(b, n, (int) gn);
-			kt.mark(CCG_K_XSUM);
-		}
 		k_hnj_update<ET><<<gn, TB, 0, st>>>(D, bs, b, n, general, exact);   // updateHNJ's Q/P pass + HNJ_popArrange
 		kt.mark(CCG_K_POP);
-		return (GEN ? 4 : 3) + xs;
+		return GEN ? 4 : 3;
 	}
 	const unsigned g = (unsigned) nj_blocks(n);
 	if(method == CCG_TREE_MN) k_nj_argmin<ET, GEN, true><<<g, TB, 0, st>>>(D, bs, b, n);
@@ -1904,14 +1895,127 @@ static int enqueue_iteration(hipStream_t st, typename Elem<ET>::T *D, double bs,
 	k_nj_join<ET><<<gn, TB, 0, st>>>(D, bs, b, n, (int) g, general, method == CCG_TREE_MN ? DBL_MAX : 1.0);
 	if(GEN) k_update_general<ET><<<1, 1024, 0, st>>>(D, bs, b, n);
 	kt.mark(CCG_K_UPDATE);
-	if(xs) {
-		k_exact_sum<><<<1, XS_NT, 0, st>>>(b, n, (int) gn);
-		kt.mark(CCG_K_XSUM);
-	}
 	k_nj_pop<ET><<<gn, TB, 0, st>>>(D, b, n, general, exact);
 	kt.mark(CCG_K_POP);
-	return (GEN ? 4 : 3) + xs;
+	return GEN ? 4 : 3;
 }
+
+#ifdef CCG_TRACE
+// the in-kernel phase stamps of a run (g_trace, g_samp, g_uamp), averaged to stderr
+static int trace_report(int method, int trace_hi, const TreeCtl &h) {
+	static unsigned long long tr[256 * NKT * 16];
+	CCG_CHECK(hipMemcpyFromSymbol(tr, HIP_SYMBOL(g_trace), sizeof(tr), 0, hipMemcpyDeviceToHost));
+	const int nk = method == CCG_TREE_DNJ ? NKT : 0;   // NJ kernels are not stamped
+	// per kernel: min block entry (15, stored inverted), block-0 phases (0..8), max block exit (14);
+	// times in us relative to the kernel's first block entry, averaged over joins
+	double acc[NKT][16] = {{0}}, gap[NKT] = {0}, itv = 0;
+	int cnt = 0;
+	bool present[NKT] = {false};   // kernels launched in this pipeline (k_dnj_select is not)
+	for(int s = 0; s < 256; ++s)
+		for(int k = 0; k < nk; ++k) present[k] = present[k] || tr[(s * NKT + k) * 16 + 15];
+	for(int s = 0; s < 256; ++s) {
+		const unsigned long long *e = tr + s * NKT * 16;
+		bool ok = true;
+		for(int k = 0; k < nk; ++k) ok = ok && (!present[k] || (e[k * 16 + 15] && e[k * 16 + 14]));
+		if(!ok) continue;
+		++cnt;
+		int k0 = 0, prev = -1;
+		while(k0 < nk && !present[k0]) ++k0;
+		for(int k = k0; k < nk; ++k) {
+			if(!present[k]) continue;
+			unsigned long long t0 = ~e[k * 16 + 15];
+			for(int p = 0; p < 15; ++p)
+				if(e[k * 16 + p]) acc[k][p] += ((double) e[k * 16 + p] - (double) t0) / 100.0;
+			if(prev >= 0) gap[k] += ((double) t0 - (double) e[prev * 16 + 14]) / 100.0;
+			prev = k;
+		}
+		if(s + 1 < 256 && tr[((s + 1) * NKT + k0) * 16 + 15]) {
+			gap[k0] += ((double) ~tr[((s + 1) * NKT + k0) * 16 + 15] - (double) e[(nk - 1) * 16 + 14]) / 100.0;
+			itv += ((double) ~tr[((s + 1) * NKT + k0) * 16 + 15] - (double) ~e[k0 * 16 + 15]) / 100.0;
+		}
+	}
+	const char *kn[NKT] = {"select", "plan/find", "scan", "join", "requeue"};
+	fprintf(stderr, "trace: %d joins at n <= %d; iteration %.2f us; serial replays %d, serial sums %d\n", cnt,
+	        trace_hi, cnt ? itv / (cnt - 1) : 0, h.serial_replays, h.serial_sums);
+	{
+		// sampled scan blocks (every 32nd): start and end relative to the kernel's first entry
+		static unsigned long long sp[256 * 64 * 3];
+		CCG_CHECK(hipMemcpyFromSymbol(sp, HIP_SYMBOL(g_samp), sizeof(sp), 0, hipMemcpyDeviceToHost));
+		double st_max = 0, en_max = 0, dur = 0, st_med = 0, stg = 0;
+		int sc = 0, jc = 0;
+		for(int s = 0; s < 256; ++s) {
+			const unsigned long long t0 = ~tr[(s * NKT + 2) * 16 + 15];
+			if(!tr[(s * NKT + 2) * 16 + 15]) continue;
+			double smax = 0, emax = 0;
+			int any = 0;
+			for(int q = 0; q < 64; ++q) {
+				const unsigned long long *e = sp + (s * 64 + q) * 3;
+				if(!e[0] || !e[2] || e[0] < t0) continue;
+				const double a = (e[0] - t0) / 100.0, z = (e[2] - t0) / 100.0;
+				smax = a > smax ? a : smax;
+				emax = z > emax ? z : emax;
+				dur += z - a;
+				if(e[1] >= e[0]) stg += (e[1] - e[0]) / 100.0;
+				st_med += a;
+				++sc;
+				any = 1;
+			}
+			if(any) {
+				st_max += smax;
+				en_max += emax;
+				++jc;
+			}
+		}
+		{
+			static unsigned long long ua[256 * 64 * 8];
+			CCG_CHECK(hipMemcpyFromSymbol(ua, HIP_SYMBOL(g_uamp), sizeof(ua), 0, hipMemcpyDeviceToHost));
+			double ud[4] = {0}, ug[4] = {0}, us0 = 0;
+			int uc[4] = {0}, gc[4] = {0}, s0c = 0;
+			for(int s = 0; s < 256; ++s) {
+				const unsigned long long t0 = ~tr[(s * NKT + 2) * 16 + 15];
+				if(!tr[(s * NKT + 2) * 16 + 15]) continue;
+				for(int q = 0; q < 64; ++q) {
+					const unsigned long long *e = ua + (s * 64 + q) * 8;
+					const unsigned long long *sp0 = sp + (s * 64 + q) * 3;
+					if(e[0] && e[0] >= t0 && sp0[0] && e[0] >= sp0[0]) {
+						us0 += (e[0] - sp0[0]) / 100.0;   // block entry -> first unit
+						++s0c;
+					}
+					for(int k = 0; k < 4; ++k) {
+						if(e[2 * k] && e[2 * k + 1] >= e[2 * k] && e[2 * k] >= t0) {
+							ud[k] += (e[2 * k + 1] - e[2 * k]) / 100.0;
+							++uc[k];
+						}
+						if(k && e[2 * k] && e[2 * k - 1] && e[2 * k] >= e[2 * k - 1] && e[2 * k] >= t0) {
+							ug[k] += (e[2 * k] - e[2 * k - 1]) / 100.0;
+							++gc[k];
+						}
+					}
+				}
+			}
+			fprintf(stderr, "  scan units (wave 0 of sampled blocks): entry->first unit %.2f us;", s0c ? us0 / s0c : 0.0);
+			for(int k = 0; k < 4; ++k)
+				fprintf(stderr, " unit%d n=%d dur %.2f gap %.2f;", k, uc[k], uc[k] ? ud[k] / uc[k] : 0.0, gc[k] ? ug[k] / gc[k] : 0.0);
+			fprintf(stderr, "\n");
+			memset(ua, 0, sizeof(ua));
+			CCG_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_uamp), ua, sizeof(ua), 0, hipMemcpyHostToDevice));
+		}
+		if(jc) fprintf(stderr, "  scan samples: %d joins, %.1f working blocks sampled/join; last start %.2f us, last end %.2f us, mean start %.2f, mean duration %.2f us (setup %.2f)\n",
+		                jc, (double) sc / jc, st_max / jc, en_max / jc, st_med / sc, dur / sc, stg / sc);
+	}
+	for(int k = 0; k < nk && cnt; ++k) {
+		if(!present[k]) continue;
+		fprintf(stderr, "  %-14s gap-before %6.2f  span %6.2f  block0:", kn[k], gap[k] / cnt, acc[k][14] / cnt);
+		for(int p = 0; p < 14; ++p) fprintf(stderr, " %6.2f", acc[k][p] / cnt);
+		fprintf(stderr, "\n");
+	}
+	return CCG_OK;
+}
+#endif
+
+// (k_exact_sum, the one-block serial-order row sum, is no longer launched: the exact row sums are split over
+// the join kernel and its consumer, xs_join_row / xs_walk_blocks.  It is still built into the engine.)
+template __global__ void k_exact_sum<>(TreeBufs b, int n, int G);
 
 static bool g_progress = false;
 
@@ -1939,22 +2043,16 @@ static int tree_run_t(ccg_ctx *ctx, const ccg_tree_args *a, void *Dd, ccg_join *
 	int rc = tree_alloc_ctx(ctx, &w, n0);
 	if(rc) return rc;
 	TreeBufs b = w.b;
-	TreeCtl init;
-	memset(&init, 0, sizeof(init));
-	init.neg = (a->flags & 2) != 0;
-	init.exact = a->exact != 0;
-	init.method = a->method;
-	init.hj = init.hi = -1;
+	TreeCtl init = tree_ctl_seed(a);
 	if(sin) {   // a resumed DNJ state: its candidate takes k_dnj_prep's place
 		init.cand = sin->cand;
 		init.cand_q = sin->Q[sin->cand];
 		init.cand_p = sin->P[sin->cand];
 	}
-	CCG_CHECK(hipMemcpyAsync(b.ctl, &init, sizeof(init), hipMemcpyHostToDevice, st));
-	long long launches = 0;
-	static thread_local KTimer kt;   // one per host thread (the CLI runs one rank per thread)
-	CCG_CHECK(hipEventRecord(ctx->ev0, st));
-	kt.init(st, a->profile != 0);
+	TreeRun<TreeCtl> run(ctx, b.ctl);
+	KTimer &kt = run.kt;
+	long long &launches = run.launches;
+	CCG_TRY(run.begin(init, a->profile != 0));
 	k_init_rows<ET><<<cdiv(n0, TB / 64), TB, 0, st>>>(D, n0, bs, b.sD, b.N, b.ctl);
 	k_init_cols<ET><<<cdiv(n0, TB), TB, 0, st>>>(D, n0, bs, b.sD, b.N, b.ctl);
 	launches += 2;
@@ -1978,24 +2076,15 @@ static int tree_run_t(ccg_ctx *ctx, const ccg_tree_args *a, void *Dd, ccg_join *
 	kt.mark(CCG_K_INIT);
 	CCG_CHECK(hipGetLastError());
 	TreeCtl h;
-	CCG_CHECK(hipMemcpyAsync(&h, b.ctl, sizeof(h), hipMemcpyDeviceToHost, st));
-	CCG_CHECK(hipStreamSynchronize(st));
+	CCG_TRY(run.read_ctl(h));
 	// GEN = false assumes N[k] == n for every row (no missing entries ever)
 	const bool general = h.has_missing != 0 || resumed_counts;
 	// the block lower bounds (DnjGrid::lb): one allocation beside the run's
-	void *lbmem = NULL;
 	if(a->method == CCG_TREE_DNJ && !general && g_grid.lb && n0 > g_grid.lb_min_n) {
-		const long long LS = (n0 + LBW - 1) / LBW;
-		const size_t lbb = ((size_t) n0 * LS * 4 + 255) & ~(size_t) 255;
-		const size_t msb = ((size_t) (LS + 1) * 8 + 255) & ~(size_t) 255;
-		const size_t ubb = ((size_t) n0 * 8 + 255) & ~(size_t) 255, skb = (size_t) (LB_SCAN + LB_HELP) * LB_SLOT * 8;
-		if(ccg_ctx_workspace(ctx, 1, lbb + msb + ubb + skb, &lbmem) == CCG_OK) {
-			b.lbm = (unsigned *) lbmem;
-			b.msd = (double *) ((char *) lbmem + lbb);
-			b.ubq = (double *) ((char *) lbmem + lbb + msb);
-			b.lbs = LS;
-			b.lbskip = (long long *) ((char *) lbmem + lbb + msb + ubb);
-			CCG_CHECK(hipMemsetAsync(b.lbskip, 0, skb, st));
+		const LbLayout lb = lb_layout(n0, n0);
+		void *lbmem = NULL;
+		if(ccg_ctx_workspace(ctx, 1, lb.bytes(), &lbmem) == CCG_OK) {
+			CCG_TRY(lb_bind(b, lbmem, lb, 0, st));
 			k_lb_init<ET><<<cdiv(n0, TB / 64), TB, 0, st>>>(D, n0, bs, b);
 			launches += 1;
 			CCG_CHECK(hipGetLastError());
@@ -2006,7 +2095,6 @@ static int tree_run_t(ccg_ctx *ctx, const ccg_tree_args *a, void *Dd, ccg_join *
 			if(!cmp_env) g_grid.cmp_blocks = cmp_share(2048);
 		} else {
 			(void) hipGetLastError();   // no room: the run goes without (the same joins)
-			lbmem = NULL;
 		}
 	}
 #ifdef CCG_TRACE
@@ -2017,19 +2105,16 @@ static int tree_run_t(ccg_ctx *ctx, const ccg_tree_args *a, void *Dd, ccg_join *
 	CCG_CHECK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_trace), zero_tr, sizeof(zero_tr), 0, hipMemcpyHostToDevice, st));
 #endif
 	int n = n0;
-	int since_check = 0;
 	long long win_rows = h.rows, win_cells = h.cells;   // ctl->rows / cells at the last check
-	bool stopped = false;
 	const int stop_n = a->max_joins > 0 && a->max_joins < n0 - 2 ? n0 - a->max_joins : 2;
 	while(n > stop_n) {
 		launches += general ? enqueue_iteration<ET, true>(st, D, bs, b, n, n == n0, a->method, a->exact, kt)
 		                    : enqueue_iteration<ET, false>(st, D, bs, b, n, n == n0, a->method, a->exact, kt);
 		CCG_CHECK(hipGetLastError());
 		--n;
-		if(++since_check == 1024) {
-			since_check = 0;
-			CCG_CHECK(hipMemcpyAsync(&h, b.ctl, sizeof(h), hipMemcpyDeviceToHost, st));
-			CCG_CHECK(hipStreamSynchronize(st));
+		bool read;
+		CCG_TRY(run.check(h, &read));
+		if(read) {
 			// the next window's scan form below 16384 taxa (DnjGrid::small_wave)
 			g_grid.small_wave = g_grid.adapt_rows && h.rows - win_rows > 1024LL * g_grid.adapt_rows;
 			g_grid.prune_on = !g_grid.prune_cells || h.cells - win_cells > 1024LL * g_grid.prune_cells;
@@ -2038,159 +2123,19 @@ static int tree_run_t(ccg_ctx *ctx, const ccg_tree_args *a, void *Dd, ccg_join *
 			if(g_progress && (n0 - n) % (16 * 1024) == 0)   // long trees (CCG_PROGRESS=1): a line per 16384 joins
 				fprintf(stderr, "ccg_tree: %d joins, n = %d, rows %lld cells %lld (reference rule %lld / %lld)\n", n0 - n,
 				        n, h.rows, h.cells, h.ref_rows, h.ref_cells);
-			if(h.done) {
-				stopped = true;
-				break;
-			}
+			if(h.done) break;
 		}
 	}
-	(void) stopped;
-	CCG_CHECK(hipEventRecord(ctx->ev1, st));
-	kt.finish();
-	CCG_CHECK(hipMemcpyAsync(&h, b.ctl, sizeof(h), hipMemcpyDeviceToHost, st));
-	CCG_CHECK(hipStreamSynchronize(st));
-	if(b.lbskip) {   // the bounded-out cells, from the per-wave slots
-		std::vector<long long> sl((size_t) (LB_SCAN + LB_HELP) * LB_SLOT);
-		// on the context's stream (a null-stream copy would wait for every blocking stream of the device)
-		CCG_CHECK(hipMemcpyAsync(sl.data(), b.lbskip, sl.size() * 8, hipMemcpyDeviceToHost, st));
-		CCG_CHECK(hipStreamSynchronize(st));
-		for(size_t x = 0; x < (size_t) LB_SCAN + LB_HELP; ++x) {
-			h.cells_lbskip += sl[x * LB_SLOT];
-			h.cells_help -= sl[x * LB_SLOT + 1];
-		}
-	}
-	float ms = 0;
-	CCG_CHECK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+	CCG_TRY(run.finish(h, n, b.joins, joins, njoins, final_n, final_d));
+	if(*final_n == 2) CCG_TRY(run.final_distance<ET>(D, bs, final_d));
+	CCG_TRY(lb_harvest(b, (size_t) LB_SCAN + LB_HELP, st, h));
 	if(getenv("CCG_XS_WHY"))   // diagnostics: why exact row sums fell back to the serial chain
 		fprintf(stderr, "xs_why: value %d nc %d nt %d stuck %d ex0 %d cap %d walk %d (chain sums %d of %d)\n",
 		        h.xs_why[0], h.xs_why[1], h.xs_why[2], h.xs_why[3], h.xs_why[4], h.xs_why[5], h.xs_why[6],
 		        h.chain_sums, h.serial_sums);
 #ifdef CCG_TRACE
-	{
-		static unsigned long long tr[256 * NKT * 16];
-		CCG_CHECK(hipMemcpyFromSymbol(tr, HIP_SYMBOL(g_trace), sizeof(tr), 0, hipMemcpyDeviceToHost));
-		const int nk = a->method == CCG_TREE_DNJ ? NKT : 0;   // NJ kernels are not stamped
-		// per kernel: min block entry (15, stored inverted), block-0 phases (0..8), max block exit (14);
-		// times in us relative to the kernel's first block entry, averaged over joins
-		double acc[NKT][16] = {{0}}, gap[NKT] = {0}, itv = 0;
-		int cnt = 0;
-		bool present[NKT] = {false};   // kernels launched in this pipeline (k_dnj_select is not)
-		for(int s = 0; s < 256; ++s)
-			for(int k = 0; k < nk; ++k) present[k] = present[k] || tr[(s * NKT + k) * 16 + 15];
-		for(int s = 0; s < 256; ++s) {
-			const unsigned long long *e = tr + s * NKT * 16;
-			bool ok = true;
-			for(int k = 0; k < nk; ++k) ok = ok && (!present[k] || (e[k * 16 + 15] && e[k * 16 + 14]));
-			if(!ok) continue;
-			++cnt;
-			int k0 = 0, prev = -1;
-			while(k0 < nk && !present[k0]) ++k0;
-			for(int k = k0; k < nk; ++k) {
-				if(!present[k]) continue;
-				unsigned long long t0 = ~e[k * 16 + 15];
-				for(int p = 0; p < 15; ++p)
-					if(e[k * 16 + p]) acc[k][p] += ((double) e[k * 16 + p] - (double) t0) / 100.0;
-				if(prev >= 0) gap[k] += ((double) t0 - (double) e[prev * 16 + 14]) / 100.0;
-				prev = k;
-			}
-			if(s + 1 < 256 && tr[((s + 1) * NKT + k0) * 16 + 15]) {
-				gap[k0] += ((double) ~tr[((s + 1) * NKT + k0) * 16 + 15] - (double) e[(nk - 1) * 16 + 14]) / 100.0;
-				itv += ((double) ~tr[((s + 1) * NKT + k0) * 16 + 15] - (double) ~e[k0 * 16 + 15]) / 100.0;
-			}
-		}
-		const char *kn[NKT] = {"select", "plan/find", "scan", "join", "requeue"};
-		fprintf(stderr, "trace: %d joins at n <= %d; iteration %.2f us; serial replays %d, serial sums %d\n", cnt,
-		        trace_hi, cnt ? itv / (cnt - 1) : 0, h.serial_replays, h.serial_sums);
-		{
-			// sampled scan blocks (every 32nd): start and end relative to the kernel's first entry
-			static unsigned long long sp[256 * 64 * 3];
-			CCG_CHECK(hipMemcpyFromSymbol(sp, HIP_SYMBOL(g_samp), sizeof(sp), 0, hipMemcpyDeviceToHost));
-			double st_max = 0, en_max = 0, dur = 0, st_med = 0, stg = 0;
-			int sc = 0, jc = 0;
-			for(int s = 0; s < 256; ++s) {
-				const unsigned long long t0 = ~tr[(s * NKT + 2) * 16 + 15];
-				if(!tr[(s * NKT + 2) * 16 + 15]) continue;
-				double smax = 0, emax = 0;
-				int any = 0;
-				for(int q = 0; q < 64; ++q) {
-					const unsigned long long *e = sp + (s * 64 + q) * 3;
-					if(!e[0] || !e[2] || e[0] < t0) continue;
-					const double a = (e[0] - t0) / 100.0, z = (e[2] - t0) / 100.0;
-					smax = a > smax ? a : smax;
-					emax = z > emax ? z : emax;
-					dur += z - a;
-					if(e[1] >= e[0]) stg += (e[1] - e[0]) / 100.0;
-					st_med += a;
-					++sc;
-					any = 1;
-				}
-				if(any) {
-					st_max += smax;
-					en_max += emax;
-					++jc;
-				}
-			}
-			{
-				static unsigned long long ua[256 * 64 * 8];
-				CCG_CHECK(hipMemcpyFromSymbol(ua, HIP_SYMBOL(g_uamp), sizeof(ua), 0, hipMemcpyDeviceToHost));
-				double ud[4] = {0}, ug[4] = {0}, us0 = 0;
-				int uc[4] = {0}, gc[4] = {0}, s0c = 0;
-				for(int s = 0; s < 256; ++s) {
-					const unsigned long long t0 = ~tr[(s * NKT + 2) * 16 + 15];
-					if(!tr[(s * NKT + 2) * 16 + 15]) continue;
-					for(int q = 0; q < 64; ++q) {
-						const unsigned long long *e = ua + (s * 64 + q) * 8;
-						const unsigned long long *sp0 = sp + (s * 64 + q) * 3;
-						if(e[0] && e[0] >= t0 && sp0[0] && e[0] >= sp0[0]) {
-							us0 += (e[0] - sp0[0]) / 100.0;   // block entry -> first unit
-							++s0c;
-						}
-						for(int k = 0; k < 4; ++k) {
-							if(e[2 * k] && e[2 * k + 1] >= e[2 * k] && e[2 * k] >= t0) {
-								ud[k] += (e[2 * k + 1] - e[2 * k]) / 100.0;
-								++uc[k];
-							}
-							if(k && e[2 * k] && e[2 * k - 1] && e[2 * k] >= e[2 * k - 1] && e[2 * k] >= t0) {
-								ug[k] += (e[2 * k] - e[2 * k - 1]) / 100.0;
-								++gc[k];
-							}
-						}
-					}
-				}
-				fprintf(stderr, "  scan units (wave 0 of sampled blocks): entry->first unit %.2f us;", s0c ? us0 / s0c : 0.0);
-				for(int k = 0; k < 4; ++k)
-					fprintf(stderr, " unit%d n=%d dur %.2f gap %.2f;", k, uc[k], uc[k] ? ud[k] / uc[k] : 0.0, gc[k] ? ug[k] / gc[k] : 0.0);
-				fprintf(stderr, "\n");
-				memset(ua, 0, sizeof(ua));
-				CCG_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_uamp), ua, sizeof(ua), 0, hipMemcpyHostToDevice));
-			}
-			if(jc) fprintf(stderr, "  scan samples: %d joins, %.1f working blocks sampled/join; last start %.2f us, last end %.2f us, mean start %.2f, mean duration %.2f us (setup %.2f)\n",
-			                jc, (double) sc / jc, st_max / jc, en_max / jc, st_med / sc, dur / sc, stg / sc);
-		}
-		for(int k = 0; k < nk && cnt; ++k) {
-			if(!present[k]) continue;
-			fprintf(stderr, "  %-14s gap-before %6.2f  span %6.2f  block0:", kn[k], gap[k] / cnt, acc[k][14] / cnt);
-			for(int p = 0; p < 14; ++p) fprintf(stderr, " %6.2f", acc[k][p] / cnt);
-			fprintf(stderr, "\n");
-		}
-	}
+	CCG_TRY(trace_report(a->method, trace_hi, h));
 #endif
-	if(h.done && h.final_n < 0) {   // k_dnj_plan's look-back timed out (never expected)
-		ccg_set_last_msg("k_dnj_plan / k_dnj_join: a block's bounded wait on another block timed out");
-		return CCG_EHIP;
-	}
-	*njoins = h.njoins;
-	*final_n = h.done ? h.final_n : n;
-	if(h.njoins) {
-		CCG_CHECK(hipMemcpyAsync(joins, b.joins, (size_t) h.njoins * sizeof(ccg_join), hipMemcpyDeviceToHost, st));
-	}
-	*final_d = -1.0;
-	if(*final_n == 2) {
-		T v;
-		CCG_CHECK(hipMemcpyAsync(&v, D, sizeof(T), hipMemcpyDeviceToHost, st));
-		CCG_CHECK(hipStreamSynchronize(st));
-		*final_d = (ET == 8 || ET == 4) ? (double) v : v / bs;
-	}
 	if(sout) {   // the loop state after the last join, as the next minQpair reads it
 		// (a finished tree, n == 2, has no next join: n = 0 as for a stopped one)
 		const bool over = h.done || n <= 2;
@@ -2216,28 +2161,18 @@ static int tree_run_t(ccg_ctx *ctx, const ccg_tree_args *a, void *Dd, ccg_join *
 			sout->cand = h2.cand;
 		}
 	}
-	if(stats) {
-		stats[0] = h.rows;
-		stats[1] = h.cells - h.cells_pruned - h.cells_lbskip;   // cells the scans loaded (listed, less the pruned / bounded-out ones)
-		stats[2] = launches;
-		stats[3] = (int64_t) (ms * 1000.0);
-		if(a->profile) {
-			for(int c = 0; c < CCG_NKSTAT; ++c) {
-				stats[4 + 2 * c] = kt.cnt[c];
-				stats[5 + 2 * c] = kt.ns[c];
-			}
-			stats[4 + 2 * CCG_NKSTAT] = h.cells_top;
-			stats[5 + 2 * CCG_NKSTAT] = h.cells_rest - h.cells_pruned - h.cells_lbskip;
-			stats[6 + 2 * CCG_NKSTAT] = h.serial_sums;
-			stats[7 + 2 * CCG_NKSTAT] = h.chain_sums;
-			stats[8 + 2 * CCG_NKSTAT] = h.cells_help;
-			stats[9 + 2 * CCG_NKSTAT] = 0;
-			stats[10 + 2 * CCG_NKSTAT] = h.ref_rows;
-			stats[11 + 2 * CCG_NKSTAT] = h.ref_cells;
-		}
-	}
-	CCG_CHECK(hipStreamSynchronize(st));
-	return CCG_OK;   // the workspaces stay with the context (ccg_ctx_workspace)
+	TreeStats s = run.stats();
+	s.rows = h.rows;
+	s.cells = h.cells - h.cells_pruned - h.cells_lbskip;   // cells the scans loaded (listed, less the pruned / bounded-out ones)
+	s.cells_top = h.cells_top;
+	s.cells_rest = h.cells_rest - h.cells_pruned - h.cells_lbskip;
+	s.serial_sums = h.serial_sums;
+	s.chain_sums = h.chain_sums;
+	s.slot8 = h.cells_help;
+	s.ref_rows = h.ref_rows;
+	s.ref_cells = h.ref_cells;
+	s.write(stats, a->profile != 0, kt);
+	return run.end();   // the workspaces stay with the context (ccg_ctx_workspace)
 }
 
 // ------------------------------------------------------------------ self-test of the exact row sum

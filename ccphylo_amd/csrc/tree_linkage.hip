@@ -32,7 +32,7 @@
 #include <string.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include "ccg_tree_common.h"
+#include "ccg_tree_run.h"
 
 #define LK_UPGMA 0
 #define LK_FF 1
@@ -683,74 +683,48 @@ static int lk_run_t(ccg_ctx *ctx, const ccg_tree_args *a, void *Dd, ccg_join *jo
 	LkCtl init;
 	memset(&init, 0, sizeof(init));
 	init.neg = (a->flags & 2) != 0;
-	CCG_CHECK(hipMemcpyAsync(b.ctl, &init, sizeof(init), hipMemcpyHostToDevice, st));
 	// the rescan grid (CCG_LK_RESCAN_BLOCKS: tests drive the one-block and the many-block form)
 	unsigned rescan_blocks = 256;
 	if(const char *e = getenv("CCG_LK_RESCAN_BLOCKS")) {
 		const int v = atoi(e);
 		if(v >= 1 && v <= 4096) rescan_blocks = (unsigned) v;
 	}
-	long long launches = 0;
-	CCG_CHECK(hipEventRecord(ctx->ev0, st));
+	TreeRun<LkCtl> run(ctx, b.ctl);
+	CCG_TRY(run.begin(init, false));   // (no per-kernel classes: a profiled run reports zeros)
 	k_lk_init_rows<ET><<<cdiv(n0, TB / 64), TB, 0, st>>>(D, n0, bs, b);
 	k_lk_init_cols<ET><<<cdiv(n0, TB), TB, 0, st>>>(D, n0, bs, b);
-	launches += 2;
+	run.launches += 2;
 	CCG_CHECK(hipGetLastError());
 	LkCtl h;
-	CCG_CHECK(hipMemcpyAsync(&h, b.ctl, sizeof(h), hipMemcpyDeviceToHost, st));
-	CCG_CHECK(hipStreamSynchronize(st));
+	CCG_TRY(run.read_ctl(h));
 	const bool general = h.has_missing != 0;
 	if(general && mode == LK_CF) {
 		ccg_set_last_msg("tree method cf: a matrix with missing (negative) cells is not supported "
 		                 "(updateCF miscounts N there, hclust.c:1188)");
 		return CCG_EUNSUP;
 	}
-	int n = n0, since_check = 0;
+	int n = n0;
 	const int stop_n = a->max_joins > 0 && a->max_joins < n0 - 2 ? n0 - a->max_joins : 2;
 	while(n > stop_n) {
 		const int first = n == n0;
-		if(mode == LK_UPGMA) launches += lk_enqueue<ET, LK_UPGMA>(st, D, bs, b, n, first, general, rescan_blocks);
-		else if(mode == LK_FF) launches += lk_enqueue<ET, LK_FF>(st, D, bs, b, n, first, general, rescan_blocks);
-		else launches += lk_enqueue<ET, LK_CF>(st, D, bs, b, n, first, general, rescan_blocks);
+		if(mode == LK_UPGMA) run.launches += lk_enqueue<ET, LK_UPGMA>(st, D, bs, b, n, first, general, rescan_blocks);
+		else if(mode == LK_FF) run.launches += lk_enqueue<ET, LK_FF>(st, D, bs, b, n, first, general, rescan_blocks);
+		else run.launches += lk_enqueue<ET, LK_CF>(st, D, bs, b, n, first, general, rescan_blocks);
 		CCG_CHECK(hipGetLastError());
 		--n;
-		if(++since_check == 1024) {
-			since_check = 0;
-			CCG_CHECK(hipMemcpyAsync(&h, b.ctl, sizeof(h), hipMemcpyDeviceToHost, st));
-			CCG_CHECK(hipStreamSynchronize(st));
-			if(h.done) break;
-		}
+		bool read;
+		CCG_TRY(run.check(h, &read));
+		if(read && h.done) break;
 	}
-	CCG_CHECK(hipEventRecord(ctx->ev1, st));
-	CCG_CHECK(hipMemcpyAsync(&h, b.ctl, sizeof(h), hipMemcpyDeviceToHost, st));
-	CCG_CHECK(hipStreamSynchronize(st));
-	float ms = 0;
-	CCG_CHECK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-	*njoins = h.njoins;
-	*final_n = h.done ? h.final_n : n;
-	if(h.njoins) CCG_CHECK(hipMemcpyAsync(joins, b.joins, (size_t) h.njoins * sizeof(ccg_join), hipMemcpyDeviceToHost, st));
-	*final_d = -1.0;
-	if(*final_n == 2) {
-		T v;
-		CCG_CHECK(hipMemcpyAsync(&v, D, sizeof(T), hipMemcpyDeviceToHost, st));
-		CCG_CHECK(hipStreamSynchronize(st));
-		*final_d = (ET == 8 || ET == 4) ? (double) v : v / bs;
-	}
-	if(stats) {
-		stats[0] = h.rows;
-		stats[1] = h.cells;
-		stats[2] = launches;
-		stats[3] = (int64_t) (ms * 1000.0);
-		if(a->profile) {
-			for(int c = 4; c < 12 + 2 * CCG_NKSTAT; ++c) stats[c] = 0;
-			stats[6 + 2 * CCG_NKSTAT] = h.serial_sums;
-			stats[7 + 2 * CCG_NKSTAT] = h.chain_sums;
-			stats[10 + 2 * CCG_NKSTAT] = h.rows;
-			stats[11 + 2 * CCG_NKSTAT] = h.cells;
-		}
-	}
-	CCG_CHECK(hipStreamSynchronize(st));
-	return CCG_OK;
+	CCG_TRY(run.finish(h, n, b.joins, joins, njoins, final_n, final_d));
+	if(*final_n == 2) CCG_TRY(run.final_distance<ET>(D, bs, final_d));
+	TreeStats s = run.stats();
+	s.rows = s.ref_rows = h.rows;
+	s.cells = s.ref_cells = h.cells;
+	s.serial_sums = h.serial_sums;
+	s.chain_sums = h.chain_sums;
+	s.write(stats, a->profile != 0, run.kt);
+	return run.end();
 }
 
 // CCG_TREE_UPGMA / CCG_TREE_CF / CCG_TREE_FF on a device LT (consumed)

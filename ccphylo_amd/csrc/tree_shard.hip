@@ -27,7 +27,7 @@
 #include <stdlib.h>
 #include <rccl/rccl.h>
 #define CCG_DNJ_NO_TRACE
-#include "ccg_tree_common.h"
+#include "ccg_tree_run.h"
 #include "ccg_shard.h"
 #include "ccg_dnj_search.h"   // k_init_hnj (initHNJ over the owned rows)
 
@@ -777,41 +777,31 @@ static int tree_shard_run_t(ccg_ctx *ctx, const ccg_tree_args *a, const ccg_coll
 	const bool hnj = a->method == CCG_TREE_HNJ;
 	if(hnj && cdiv(n0, TB) > SH_GRID) return CCG_EINVAL;   // the minQ partials (one per 256 rows)
 	const ShnLayout L(n0, coll_in->world, ET, hnj);
-	const size_t rec_b = L.rec_b, sz = L.sz;
-	const size_t o_sD = L.o_sD, o_c = L.o_c, o_N = L.o_N, o_ws = L.o_ws, o_wa = L.o_wa, o_wc = L.o_wc, o_we = L.o_we;
-	const size_t o_qp = L.o_qp, o_fp = L.o_fp, o_j = L.o_j, o_ctl = L.o_ctl, o_F = L.o_F, o_rec = L.o_rec;
-	const size_t o_X = L.o_X, o_Xm = L.o_Xm, o_xa = L.o_xa, o_xb = L.o_xb, o_xcr = L.o_xcr, o_xt = L.o_xt;
-	const size_t o_rp = L.o_rp, o_is = L.o_is;
-	char *m;
-	if(hipMalloc((void **) &m, sz) != hipSuccess) return CCG_ENOMEM;
+	DevMem mem;
+	if(!mem.alloc(L.sz)) return CCG_ENOMEM;
+	char *m = mem.p;
 	size_t hcap = sh_init_host_bytes(n0, coll_in->world);
 	if((size_t) 2 * n0 * ET > hcap) hcap = (size_t) 2 * n0 * ET;
-	if(rec_b + (size_t) n0 * ET + 16 > hcap) hcap = rec_b + (size_t) n0 * ET + 16;
-	unsigned char *h = NULL;
-	if(coll_in->host_staged && hipHostMalloc((void **) &h, hcap) != hipSuccess) {
-		hipFree(m);
-		return CCG_ENOMEM;
-	}
-	int rc = CCG_OK;
-	static thread_local KTimer kt;   // one per host thread (the CLI runs one rank per thread)
-	CollRun cr = {coll_in, st, h, &kt};
+	if(L.rec_b + (size_t) n0 * ET + 16 > hcap) hcap = L.rec_b + (size_t) n0 * ET + 16;
+	PinnedMem hm;
+	if(coll_in->host_staged && !hm.alloc(hcap)) return CCG_ENOMEM;
 	TreeBufs b;
 	memset(&b, 0, sizeof(b));
-	b.sD = (double *) (m + o_sD);
-	b.contrib = (double *) (m + o_c);
-	b.N = (int *) (m + o_N);
-	b.wsum = (double *) (m + o_ws);
-	b.wabs = (double *) (m + o_wa);
-	b.wcnt = (int *) (m + o_wc);
-	b.wexp = (int *) (m + o_we);
-	b.qpart = (double *) (m + o_qp);
-	b.fpart = (long long *) (m + o_fp);
-	b.joins = (ccg_join *) (m + o_j);
-	b.ctl = (TreeCtl *) (m + o_ctl);
-	b.xagg = (unsigned long long *) (m + o_xa);
-	b.xblk = (XsBlk *) (m + o_xb);
-	b.xcr = (XsCross *) (m + o_xcr);
-	b.xti = (XsTie *) (m + o_xt);
+	b.sD = (double *) (m + L.o_sD);
+	b.contrib = (double *) (m + L.o_c);
+	b.N = (int *) (m + L.o_N);
+	b.wsum = (double *) (m + L.o_ws);
+	b.wabs = (double *) (m + L.o_wa);
+	b.wcnt = (int *) (m + L.o_wc);
+	b.wexp = (int *) (m + L.o_we);
+	b.qpart = (double *) (m + L.o_qp);
+	b.fpart = (long long *) (m + L.o_fp);
+	b.joins = (ccg_join *) (m + L.o_j);
+	b.ctl = (TreeCtl *) (m + L.o_ctl);
+	b.xagg = (unsigned long long *) (m + L.o_xa);
+	b.xblk = (XsBlk *) (m + L.o_xb);
+	b.xcr = (XsCross *) (m + L.o_xcr);
+	b.xti = (XsTie *) (m + L.o_xt);
 	if(hnj) {
 		b.Q = (double *) (m + L.o_Q);
 		b.P = (int *) (m + L.o_P);
@@ -820,148 +810,77 @@ static int tree_shard_run_t(ccg_ctx *ctx, const ccg_tree_args *a, const ccg_coll
 		b.cfq = (double *) (m + L.o_cq);
 		b.cfp = (int *) (m + L.o_cp);
 	}
-	long long *F = (long long *) (m + o_F);
-	ShRec *rec = (ShRec *) (m + o_rec);
-	T *X = (T *) (m + o_X), *Xm = (T *) (m + o_Xm);
-	void *rp = m + o_rp;
+	long long *F = (long long *) (m + L.o_F);
+	ShRec *rec = (ShRec *) (m + L.o_rec);
+	T *X = (T *) (m + L.o_X), *Xm = (T *) (m + L.o_Xm);
 	ShInitStat istat = {0, 0};
-	long long *hF = (long long *) malloc((size_t) (nseg0 + 2) * 8);
-	TreeCtl init, hc;
-	long long launches = 0;
-	int n = n0;
-	float ms = 0;
-	memset(&init, 0, sizeof(init));
-	init.neg = (a->flags & 2) != 0;
-	init.exact = a->exact != 0;
-	init.method = a->method;
-	init.hj = init.hi = -1;
-#define SH_TRY(x)                    \
-	do {                             \
-		if((rc = (x)) != CCG_OK) goto out; \
-	} while(0)
-#define SH_HIP(x)                                                     \
-	do {                                                              \
-		hipError_t e_ = (x);                                          \
-		if(e_ != hipSuccess) {                                        \
-			ccg_set_last_error(e_, #x, __FILE__, __LINE__);          \
-			rc = e_ == hipErrorOutOfMemory ? CCG_ENOMEM : CCG_EHIP;  \
-			goto out;                                                 \
-		}                                                             \
-	} while(0)
-	if(!hF) {
-		rc = CCG_ENOMEM;
-		goto out;
-	}
+	std::vector<long long> hF((size_t) nseg0 + 2);
 	hF[0] = 0;
 	for(int s = 0; s <= nseg0; ++s) hF[s + 1] = hF[s] + sh_first(s, sh);
-	SH_HIP(hipMemsetAsync(m, 0, sz, st));
-	SH_HIP(hipMemcpyAsync(F, hF, (size_t) (nseg0 + 2) * 8, hipMemcpyHostToDevice, st));
-	SH_HIP(hipMemcpyAsync(b.ctl, &init, sizeof(init), hipMemcpyHostToDevice, st));
-	SH_HIP(hipEventRecord(ctx->ev0, st));
-	kt.init(st, a->profile != 0);
-	{
-		int missing = 0;
-		SH_TRY(sh_init_summad<ET>(D, n0, bs, sh, cr, st, rp, m + o_is, b, &launches, &missing, &istat));
-		if(missing) {
-			rc = CCG_EUNSUP;   // the missing-entry quirks of updateD run on one GPU only
-			goto out;
-		}
-	}
+	const TreeCtl init = tree_ctl_seed(a);
+	TreeRun<TreeCtl> run(ctx, b.ctl);   // (after the memory: it waits for the stream before that is freed)
+	KTimer &kt = run.kt;
+	CollRun cr = {coll_in, st, hm.p, &kt};
+	CCG_CHECK(hipMemsetAsync(m, 0, L.sz, st));
+	CCG_CHECK(hipMemcpyAsync(F, hF.data(), hF.size() * 8, hipMemcpyHostToDevice, st));
+	CCG_TRY(run.begin(init, a->profile != 0));
+	int missing = 0;
+	CCG_TRY(sh_init_summad<ET>(D, n0, bs, sh, cr, st, m + L.o_rp, m + L.o_is, b, &run.launches, &missing, &istat));
+	if(missing) return CCG_EUNSUP;   // the missing-entry quirks of updateD run on one GPU only
 	if(hnj) {   // initHNJ (hclust.c:56) over the owned rows
 		k_init_hnj<ET><<<cdiv(n0, TB / 64), TB, 0, st>>>(sh, D, n0, bs, b.sD, b.N, b.Q, b.P);
-		SH_HIP(hipGetLastError());
-		++launches;
+		CCG_CHECK(hipGetLastError());
+		++run.launches;
 	}
-	{
-		int since_check = 0;
-		const int stop_n = a->max_joins > 0 && a->max_joins < n0 - 2 ? n0 - a->max_joins : 2;
-		while(n > stop_n) {
-			T *Xmr = (T *) ((char *) rec + rec_b);   // row n-1, gathered with the records
-			k_sh_xm<ET><<<cdiv(n - 1, TB), TB, 0, st>>>(D, n, sh, Xmr);
-			const unsigned gn = cdiv(n, TB);
-			int G = 0;
-			if(hnj) {   // minQ over the owned rows' (Q, P)
-				G = (int) gn;
-				k_sh_hnj_argmin<><<<gn, TB, 0, st>>>(b, n, sh);
-			} else {
-				const int nlb = sh_nlb(n, sh), nseg = (int) cdiv(n - 1, NJ_SEG);
-				int sstar = 0;
-				while(sstar < nseg && hF[sstar + 1] - hF[sstar] < nlb) ++sstar;
-				const long long tiles = (long long) sstar * nlb - hF[sstar];
-				G = (int) (tiles < SH_GRID ? tiles : SH_GRID);
-				if(G > 0) k_sh_argmin<ET><<<G, TB, 0, st>>>(D, bs, b, n, sh, F, nlb, sstar, tiles);
-			}
-			const double q0 = hnj ? DBL_MAX : 1.0;   // HNJ's minQ starts at DBL_MAX, NJ's initQ at 1
-			k_sh_fold<<<1, TB, 0, st>>>(b, G, sh, rec, q0);
-			kt.mark(CCG_K_ARGMIN);
-			SH_TRY(cr.allreduce(rec, rec_b + (size_t) (n - 1) * ET));
-			k_sh_lines<ET><<<gn, TB, 0, st>>>(D, b, n, sh, rec, X, q0);
-			kt.mark(CCG_K_UPDATE);
-			SH_TRY(cr.allreduce(X, (size_t) 2 * n * ET));
-			k_sh_join<ET><<<gn, TB, 0, st>>>(D, bs, b, n, sh, rec, X, Xmr, q0, hnj);
-			kt.mark(CCG_K_UPDATE);
-			if(hnj) k_sh_hnj<ET><<<gn, TB, 0, st>>>(D, bs, b, n, sh, X, Xmr);
-			else k_sh_pop<ET><<<gn, TB, 0, st>>>(D, b, n, sh, Xmr);
-			kt.mark(CCG_K_POP);
-			SH_HIP(hipGetLastError());
-			launches += (G > 0) + 5;   // k_sh_xm, fold, lines, join, pop
-			--n;
-			if(++since_check == 1024) {
-				since_check = 0;
-				SH_HIP(hipMemcpyAsync(&hc, b.ctl, sizeof(hc), hipMemcpyDeviceToHost, st));
-				SH_HIP(hipStreamSynchronize(st));
-				if(hc.done) break;
-			}
+	TreeCtl hc;
+	int n = n0;
+	const int stop_n = a->max_joins > 0 && a->max_joins < n0 - 2 ? n0 - a->max_joins : 2;
+	while(n > stop_n) {
+		T *Xmr = (T *) ((char *) rec + L.rec_b);   // row n-1, gathered with the records
+		k_sh_xm<ET><<<cdiv(n - 1, TB), TB, 0, st>>>(D, n, sh, Xmr);
+		const unsigned gn = cdiv(n, TB);
+		int G = 0;
+		if(hnj) {   // minQ over the owned rows' (Q, P)
+			G = (int) gn;
+			k_sh_hnj_argmin<><<<gn, TB, 0, st>>>(b, n, sh);
+		} else {
+			const int nlb = sh_nlb(n, sh), nseg = (int) cdiv(n - 1, NJ_SEG);
+			int sstar = 0;
+			while(sstar < nseg && hF[sstar + 1] - hF[sstar] < nlb) ++sstar;
+			const long long tiles = (long long) sstar * nlb - hF[sstar];
+			G = (int) (tiles < SH_GRID ? tiles : SH_GRID);
+			if(G > 0) k_sh_argmin<ET><<<G, TB, 0, st>>>(D, bs, b, n, sh, F, nlb, sstar, tiles);
 		}
+		const double q0 = hnj ? DBL_MAX : 1.0;   // HNJ's minQ starts at DBL_MAX, NJ's initQ at 1
+		k_sh_fold<<<1, TB, 0, st>>>(b, G, sh, rec, q0);
+		kt.mark(CCG_K_ARGMIN);
+		CCG_TRY(cr.allreduce(rec, L.rec_b + (size_t) (n - 1) * ET));
+		k_sh_lines<ET><<<gn, TB, 0, st>>>(D, b, n, sh, rec, X, q0);
+		kt.mark(CCG_K_UPDATE);
+		CCG_TRY(cr.allreduce(X, (size_t) 2 * n * ET));
+		k_sh_join<ET><<<gn, TB, 0, st>>>(D, bs, b, n, sh, rec, X, Xmr, q0, hnj);
+		kt.mark(CCG_K_UPDATE);
+		if(hnj) k_sh_hnj<ET><<<gn, TB, 0, st>>>(D, bs, b, n, sh, X, Xmr);
+		else k_sh_pop<ET><<<gn, TB, 0, st>>>(D, b, n, sh, Xmr);
+		kt.mark(CCG_K_POP);
+		CCG_CHECK(hipGetLastError());
+		run.launches += (G > 0) + 5;   // k_sh_xm, fold, lines, join, pop
+		--n;
+		bool read;
+		CCG_TRY(run.check(hc, &read));
+		if(read && hc.done) break;
 	}
-	SH_HIP(hipEventRecord(ctx->ev1, st));
-	kt.finish();
-	SH_HIP(hipMemcpyAsync(&hc, b.ctl, sizeof(hc), hipMemcpyDeviceToHost, st));
-	SH_HIP(hipStreamSynchronize(st));
-	SH_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-	*njoins = hc.njoins;
-	*final_n = hc.done ? hc.final_n : n;
-	if(hc.njoins) {
-		SH_HIP(hipMemcpyAsync(joins, b.joins, (size_t) hc.njoins * sizeof(ccg_join), hipMemcpyDeviceToHost, st));
-	}
-	*final_d = -1.0;
+	CCG_TRY(run.finish(hc, n, b.joins, joins, njoins, final_n, final_d));
 	if(*final_n == 2) {
 		// D(1, 0): row 1 is in band 0, owned by rank 0
-		SH_TRY(cr.bcast(sh.rank == 0 ? (const void *) (D + sh.off(1)) : NULL, Xm, ET, 0));
-		T v;
-		SH_HIP(hipMemcpyAsync(&v, Xm, sizeof(T), hipMemcpyDeviceToHost, st));
-		SH_HIP(hipStreamSynchronize(st));
-		*final_d = (ET == 8 || ET == 4) ? (double) v : v / bs;
+		CCG_TRY(cr.bcast(sh.rank == 0 ? (const void *) (D + sh.off(1)) : NULL, Xm, ET, 0));
+		CCG_TRY(run.final_distance<ET>(Xm, bs, final_d));
 	}
-	if(stats) {
-		stats[0] = 0;
-		stats[1] = 0;
-		stats[2] = launches;
-		stats[3] = (int64_t) (ms * 1000.0);
-		if(a->profile) {
-			for(int c = 0; c < CCG_NKSTAT; ++c) {
-				stats[4 + 2 * c] = kt.cnt[c];
-				stats[5 + 2 * c] = kt.ns[c];
-			}
-			stats[4 + 2 * CCG_NKSTAT] = 0;
-			stats[5 + 2 * CCG_NKSTAT] = 0;
-			stats[6 + 2 * CCG_NKSTAT] = 0;
-			stats[7 + 2 * CCG_NKSTAT] = 0;
-			stats[8 + 2 * CCG_NKSTAT] = istat.coll_bytes;
-			stats[9 + 2 * CCG_NKSTAT] = istat.hard;
-			stats[10 + 2 * CCG_NKSTAT] = 0;
-			stats[11 + 2 * CCG_NKSTAT] = 0;
-		}
-	}
-out:
-#undef SH_TRY
-#undef SH_HIP
-	if(rc != CCG_OK) kt.on = false;
-	hipStreamSynchronize(st);
-	free(hF);
-	if(h) hipHostFree(h);
-	hipFree(m);
-	return rc;
+	TreeStats s = run.stats();
+	s.slot8 = istat.coll_bytes;
+	s.hard_columns = istat.hard;
+	s.write(stats, a->profile != 0, kt);
+	return run.end();
 }
 
 // tree_shard_dnj.hip

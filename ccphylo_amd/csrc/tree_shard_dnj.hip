@@ -786,6 +786,26 @@ struct ShdLayout {
 
 size_t ccg_shard_dnj_bytes(int n, int world, int es) { return ccg_tree_bytes(n) + ShdLayout(n, world, es).sz; }
 
+// diagnostic (CCG_PICK_TS): k_shd_pick's phase stamps (s_memrealtime), averaged to stderr
+static void pick_ts_report(const unsigned long long *dbg, hipStream_t st) {
+	static thread_local unsigned long long hd[1024 * 8];
+	if(hipMemcpyAsync(hd, dbg, sizeof(hd), hipMemcpyDeviceToHost, st) != hipSuccess ||
+	   hipStreamSynchronize(st) != hipSuccess)
+		memset(hd, 0, sizeof(hd));
+	double acc[8] = {0};
+	int cnt = 0;
+	for(int s_ = 0; s_ < 1024; ++s_) {
+		const unsigned long long *t_ = hd + s_ * 8;
+		if(!t_[0] || !t_[5]) continue;
+		for(int p_ = 1; p_ < 6; ++p_) acc[p_] += (double) (t_[p_] - t_[p_ - 1]) * 10.0;
+		acc[6] += (double) t_[6];
+		++cnt;
+	}
+	if(cnt)
+		fprintf(stderr, "pick phases over %d joins (ns): entry->loads %.0f, count+scan %.0f, entries %.0f, replay %.0f, gather %.0f; total entries %.1f\n",
+		        cnt, acc[1] / cnt, acc[2] / cnt, acc[3] / cnt, acc[4] / cnt, acc[5] / cnt, acc[6] / cnt);
+}
+
 template <int ET>
 static int tree_shard_dnj_run_t(ccg_ctx *ctx, const ccg_tree_args *a, const ccg_coll *coll, void *Dd,
                                 ccg_join *joins, int *njoins, int *final_n, double *final_d, int64_t *stats) {
@@ -795,236 +815,122 @@ static int tree_shard_dnj_run_t(ccg_ctx *ctx, const ccg_tree_args *a, const ccg_
 	const double bs = a->byteScale;
 	hipStream_t st = ctx->stream;
 	const Shard sh = {coll->rank, coll->world};
-	int rc;
 	TreeWork w;
-	if((rc = ccg_tree_alloc(&w, n0, st))) return rc;
+	CCG_TRY(ccg_tree_alloc(&w, n0, st));
+	DevMem wmem(w.mem), mem, lbmem, dbgmem;
 	TreeBufs b = w.b;
 	const ShdLayout L(n0, coll->world, ET);
 	const RecSlot rs0 = rec_slot(n0, coll->world);
-	const size_t o_R = L.o_R, o_X = L.o_X, o_Xm = L.o_Xm, o_Sl = L.o_Sl, o_G = L.o_G, o_Xj = L.o_Xj, o_pf = L.o_pf;
-	const size_t o_pa = L.o_pa, o_pc = L.o_pc, o_rp = L.o_rp, o_is = L.o_is, sz = L.sz;
-	char *m = NULL;
-	unsigned char *h = NULL;
-	if(hipMalloc((void **) &m, sz) != hipSuccess) {
-		hipFree(w.mem);
-		return CCG_ENOMEM;
-	}
+	if(!mem.alloc(L.sz)) return CCG_ENOMEM;
+	char *m = mem.p;
 	size_t hcap = sh_init_host_bytes(n0, coll->world);
 	if((size_t) 3 * n0 * ET > hcap) hcap = (size_t) 3 * n0 * ET;
 	if(rec_bytes(n0) > hcap) hcap = rec_bytes(n0);
 	if((size_t) coll->world * rs0.bytes > hcap) hcap = (size_t) coll->world * rs0.bytes;
-	if(coll->host_staged && hipHostMalloc((void **) &h, hcap) != hipSuccess) {
-		hipFree(m);
-		hipFree(w.mem);
-		return CCG_ENOMEM;
-	}
-	static thread_local KTimer kt;   // one per host thread (the CLI runs one rank per thread)
-	CollRun cr = {coll, st, h, &kt};
+	PinnedMem hm;
+	if(coll->host_staged && !hm.alloc(hcap)) return CCG_ENOMEM;
 	DnjGrid grid;
 	grid.load();
-	void *R = m + o_R, *Sl = m + o_Sl, *G = m + o_G;   // initHNJ's gather; this rank's record slot; the gathered slots
-	T *X = (T *) (m + o_X), *Xm = (T *) (m + o_Xm), *Xj = (T *) (m + o_Xj);
+	void *R = m + L.o_R, *Sl = m + L.o_Sl, *G = m + L.o_G;   // initHNJ's gather; this rank's record slot; the gathered slots
+	T *X = (T *) (m + L.o_X), *Xm = (T *) (m + L.o_Xm), *Xj = (T *) (m + L.o_Xj);
 	ShInitStat istat = {0, 0};
-	unsigned char *pflag = (unsigned char *) (m + o_pf), *pacc = (unsigned char *) (m + o_pa);
-	unsigned *pcnt = (unsigned *) (m + o_pc);
+	unsigned char *pflag = (unsigned char *) (m + L.o_pf), *pacc = (unsigned char *) (m + L.o_pa);
+	unsigned *pcnt = (unsigned *) (m + L.o_pc);
 	unsigned long long *dbg = NULL;
-	void *lbmem = NULL;
-	// diagnostic: k_shd_pick's phase stamps (s_memrealtime), averaged to stderr
-	if(getenv("CCG_PICK_TS")) {
-		if(hipMalloc((void **) &dbg, 1024 * 8 * 8) != hipSuccess) dbg = NULL;
-		else if(hipMemsetAsync(dbg, 0, 1024 * 8 * 8, st) != hipSuccess) {
-			hipFree(dbg);
-			dbg = NULL;
-		}
-	}
-	TreeCtl init, hc;
-	long long launches = 0;
-	int n = n0;
-	float ms = 0;
-	memset(&init, 0, sizeof(init));
-	init.neg = (a->flags & 2) != 0;
-	init.exact = a->exact != 0;
-	init.method = a->method;
-#define SD_TRY(x)                          \
-	do {                                   \
-		if((rc = (x)) != CCG_OK) goto out; \
-	} while(0)
-#define SD_HIP(x)                                                    \
-	do {                                                             \
-		hipError_t e_ = (x);                                         \
-		if(e_ != hipSuccess) {                                       \
-			ccg_set_last_error(e_, #x, __FILE__, __LINE__);         \
-			rc = e_ == hipErrorOutOfMemory ? CCG_ENOMEM : CCG_EHIP; \
-			goto out;                                                \
-		}                                                            \
-	} while(0)
-	SD_HIP(hipMemsetAsync(m, 0, sz, st));
-	SD_HIP(hipMemcpyAsync(b.ctl, &init, sizeof(init), hipMemcpyHostToDevice, st));
-	SD_HIP(hipEventRecord(ctx->ev0, st));
-	kt.init(st, a->profile != 0);
-	{
-		int missing = 0;
-		SD_TRY(sh_init_summad<ET>(D, n0, bs, sh, cr, st, m + o_rp, m + o_is, b, &launches, &missing, &istat));
-		if(missing) {
-			rc = CCG_EUNSUP;   // the missing-entry quirks of updateD run on one GPU only
-			goto out;
-		}
-	}
-	SD_TRY(shd_init_hnj<ET>(D, n0, bs, sh, cr, st, b, R));
-	launches += 2;
+	if(getenv("CCG_PICK_TS") && dbgmem.alloc(1024 * 8 * 8) && hipMemsetAsync(dbgmem.p, 0, 1024 * 8 * 8, st) == hipSuccess)
+		dbg = (unsigned long long *) dbgmem.p;
+	const TreeCtl init = tree_ctl_seed(a);
+	TreeRun<TreeCtl> run(ctx, b.ctl);   // (after the memory: it waits for the stream before that is freed)
+	KTimer &kt = run.kt;
+	CollRun cr = {coll, st, hm.p, &kt};
+	CCG_CHECK(hipMemsetAsync(m, 0, L.sz, st));
+	CCG_TRY(run.begin(init, a->profile != 0));
+	int missing = 0;
+	CCG_TRY(sh_init_summad<ET>(D, n0, bs, sh, cr, st, m + L.o_rp, m + L.o_is, b, &run.launches, &missing, &istat));
+	if(missing) return CCG_EUNSUP;   // the missing-entry quirks of updateD run on one GPU only
+	CCG_TRY(shd_init_hnj<ET>(D, n0, bs, sh, cr, st, b, R));
+	run.launches += 2;
 	// the block lower bounds (DnjGrid::lb, as the single engine): a line per
 	// owned row, the sD maxima and the thresholds replicated
 	if(grid.lb && n0 > grid.lb_min_n) {
-		const long long LS = (n0 + LBW - 1) / LBW, own = (long long) cdiv(cdiv(n0, 8), sh.world) * 8;
-		const size_t lbb = ((size_t) own * LS * 4 + 255) & ~(size_t) 255;
-		const size_t msb = ((size_t) (LS + 1) * 8 + 255) & ~(size_t) 255;
-		const size_t ubb = ((size_t) n0 * 8 + 255) & ~(size_t) 255, skb = (size_t) (LB_SCAN + LB_HELP) * LB_SLOT * 8;
-		if(hipMalloc(&lbmem, lbb + msb + ubb + skb) == hipSuccess) {
-			b.lbm = (unsigned *) lbmem;
-			b.msd = (double *) ((char *) lbmem + lbb);
-			b.ubq = (double *) ((char *) lbmem + lbb + msb);
-			b.lbs = LS;
-			b.lbw = sh.world;
-			b.lbskip = (long long *) ((char *) lbmem + lbb + msb + ubb);
-			SD_HIP(hipMemsetAsync(b.lbskip, 0, skb, st));
+		const LbLayout lb = lb_layout(n0, (long long) cdiv(cdiv(n0, 8), sh.world) * 8);
+		if(lbmem.alloc(lb.bytes())) {   // (no room: the run goes without, the same joins)
+			CCG_TRY(lb_bind(b, lbmem.p, lb, sh.world, st));
 			k_shd_lb_init<ET><<<cdiv(n0, TB / 64), TB, 0, st>>>(D, n0, bs, b, sh);
-			SD_HIP(hipGetLastError());
-			launches += 1;
-		} else {
-			(void) hipGetLastError();   // no room: the run goes without (the same joins)
-			lbmem = NULL;
+			CCG_CHECK(hipGetLastError());
+			run.launches += 1;
 		}
 	}
-	{
-		int since_check = 0;
-		const int stop_n = a->max_joins > 0 && a->max_joins < n0 - 2 ? n0 - a->max_joins : 2;
-		while(n > stop_n) {
-			const unsigned gn = cdiv(n, TB), gp = cdiv(n, PICK_T) < PICK_MAXB ? cdiv(n, PICK_T) : PICK_MAXB;
-			T *Xmr = X + 2 * (size_t) n;   // row n-1, gathered with lines i and j
-			const int seg = grid.seg(n);
-			// one-phase search (k_dnj_plan): each rank lists the S rows and the
-			// rows below S it owns, under the bound of its own S rows' partner
-			// cells (a subset of S: looser, still exact after the replay)
-			// the listing over a grid of blocks with the decoupled look-back past 15361 taxa, as on one GPU:
-			// every rank walks all n rows for its owned ones (round 6: one block took 140 us per join at
-			// 200k, tools/shard_cost.py)
-			const unsigned gpl = grid.plan_blocks(n);
-			if(grid.bands(n)) k_dnj_plan<ET, false, Shard, true><<<gpl, TBF, 0, st>>>(D, bs, b, n, n == n0, sh, seg, grid.top(n), grid.bands(n), grid.plan_flags());
-			else k_dnj_plan<ET, false, Shard, false><<<gpl, TBF, 0, st>>>(D, bs, b, n, n == n0, sh, seg, grid.top(n), 0, grid.plan_flags());
-			kt.mark(CCG_K_FIND);
-			{
-				// the scan of this join's form; each kernel instantiation is named once
-				const ScanForm f = dnj_scan_form_shard(grid, n, ET, b.lbm != NULL);
-				const RecTail<ET> rt{D, sh, Sl, pcnt};
-				switch(f.kernel) {
-					case SCAN_WAVE16:
-						if(f.lb && f.stream) k_dnj_scan_v<ET, Shard, RecTail<ET>, true, 0, false, true><<<f.grid, TB, 0, st>>>(D, bs, b, n, sh, seg, rt);
-						else if(f.lb) k_dnj_scan_v<ET, Shard, RecTail<ET>, false, 0, false, true><<<f.grid, TB, 0, st>>>(D, bs, b, n, sh, seg, rt);
-						else if(f.stream) k_dnj_scan_v<ET, Shard, RecTail<ET>, true><<<f.grid, TB, 0, st>>>(D, bs, b, n, sh, seg, rt);
-						else k_dnj_scan_v<ET, Shard, RecTail<ET>><<<f.grid, TB, 0, st>>>(D, bs, b, n, sh, seg, rt);
-						break;
-					case SCAN_WAVE: k_dnj_scan_w<ET, false, Shard, RecTail<ET>><<<f.grid, TB, 0, st>>>(D, bs, b, n, sh, seg, rt); break;
-					default: k_dnj_scan<ET, false><<<f.grid, TB, 0, st>>>(D, bs, b, n, sh, seg, rt);
-				}
-			}
-			kt.mark(CCG_K_REST);
-			SD_TRY(cr.allgather(Sl, G, rec_slot(n, sh.world).bytes));
-			k_shd_pick<ET><<<gp, PICK_T, 0, st>>>(D, b, n, sh, G, X, pacc, pflag, n0, dbg);
-			kt.mark(CCG_K_UPDATE);
-			SD_TRY(cr.allreduce(X, (size_t) 3 * n * ET));
-			k_shd_join<ET><<<gn, TB, 0, st>>>(D, bs, b, n, sh, X, Xmr, Xj, pflag);
-			kt.mark(CCG_K_UPDATE);
-			if(grid.bands(n - 1)) k_shd_requeue<ET, true><<<gn, TB, 0, st>>>(D, bs, b, n, sh, Xmr, Xj, Sl);
-			else k_shd_requeue<ET, false><<<gn, TB, 0, st>>>(D, bs, b, n, sh, Xmr, Xj, Sl);
-			kt.mark(CCG_K_REQUEUE);
-			SD_HIP(hipGetLastError());
-			launches += 5;
-			--n;
-			if(++since_check == 1024) {
-				since_check = 0;
-				SD_HIP(hipMemcpyAsync(&hc, b.ctl, sizeof(hc), hipMemcpyDeviceToHost, st));
-				SD_HIP(hipStreamSynchronize(st));
-				if(hc.done) break;
+	TreeCtl hc;
+	int n = n0;
+	const int stop_n = a->max_joins > 0 && a->max_joins < n0 - 2 ? n0 - a->max_joins : 2;
+	while(n > stop_n) {
+		const unsigned gn = cdiv(n, TB), gp = cdiv(n, PICK_T) < PICK_MAXB ? cdiv(n, PICK_T) : PICK_MAXB;
+		T *Xmr = X + 2 * (size_t) n;   // row n-1, gathered with lines i and j
+		const int seg = grid.seg(n);
+		// one-phase search (k_dnj_plan): each rank lists the S rows and the
+		// rows below S it owns, under the bound of its own S rows' partner
+		// cells (a subset of S: looser, still exact after the replay)
+		// the listing over a grid of blocks with the decoupled look-back past 15361 taxa, as on one GPU:
+		// every rank walks all n rows for its owned ones (round 6: one block took 140 us per join at
+		// 200k, tools/shard_cost.py)
+		const unsigned gpl = grid.plan_blocks(n);
+		if(grid.bands(n)) k_dnj_plan<ET, false, Shard, true><<<gpl, TBF, 0, st>>>(D, bs, b, n, n == n0, sh, seg, grid.top(n), grid.bands(n), grid.plan_flags());
+		else k_dnj_plan<ET, false, Shard, false><<<gpl, TBF, 0, st>>>(D, bs, b, n, n == n0, sh, seg, grid.top(n), 0, grid.plan_flags());
+		kt.mark(CCG_K_FIND);
+		{
+			// the scan of this join's form; each kernel instantiation is named once
+			const ScanForm f = dnj_scan_form_shard(grid, n, ET, b.lbm != NULL);
+			const RecTail<ET> rt{D, sh, Sl, pcnt};
+			switch(f.kernel) {
+				case SCAN_WAVE16:
+					if(f.lb && f.stream) k_dnj_scan_v<ET, Shard, RecTail<ET>, true, 0, false, true><<<f.grid, TB, 0, st>>>(D, bs, b, n, sh, seg, rt);
+					else if(f.lb) k_dnj_scan_v<ET, Shard, RecTail<ET>, false, 0, false, true><<<f.grid, TB, 0, st>>>(D, bs, b, n, sh, seg, rt);
+					else if(f.stream) k_dnj_scan_v<ET, Shard, RecTail<ET>, true><<<f.grid, TB, 0, st>>>(D, bs, b, n, sh, seg, rt);
+					else k_dnj_scan_v<ET, Shard, RecTail<ET>><<<f.grid, TB, 0, st>>>(D, bs, b, n, sh, seg, rt);
+					break;
+				case SCAN_WAVE: k_dnj_scan_w<ET, false, Shard, RecTail<ET>><<<f.grid, TB, 0, st>>>(D, bs, b, n, sh, seg, rt); break;
+				default: k_dnj_scan<ET, false><<<f.grid, TB, 0, st>>>(D, bs, b, n, sh, seg, rt);
 			}
 		}
+		kt.mark(CCG_K_REST);
+		CCG_TRY(cr.allgather(Sl, G, rec_slot(n, sh.world).bytes));
+		k_shd_pick<ET><<<gp, PICK_T, 0, st>>>(D, b, n, sh, G, X, pacc, pflag, n0, dbg);
+		kt.mark(CCG_K_UPDATE);
+		CCG_TRY(cr.allreduce(X, (size_t) 3 * n * ET));
+		k_shd_join<ET><<<gn, TB, 0, st>>>(D, bs, b, n, sh, X, Xmr, Xj, pflag);
+		kt.mark(CCG_K_UPDATE);
+		if(grid.bands(n - 1)) k_shd_requeue<ET, true><<<gn, TB, 0, st>>>(D, bs, b, n, sh, Xmr, Xj, Sl);
+		else k_shd_requeue<ET, false><<<gn, TB, 0, st>>>(D, bs, b, n, sh, Xmr, Xj, Sl);
+		kt.mark(CCG_K_REQUEUE);
+		CCG_CHECK(hipGetLastError());
+		run.launches += 5;
+		--n;
+		bool read;
+		CCG_TRY(run.check(hc, &read));
+		if(read && hc.done) break;
 	}
-	SD_HIP(hipEventRecord(ctx->ev1, st));
-	kt.finish();
-	if(dbg) {
-		static thread_local unsigned long long hd[1024 * 8];
-		if(hipMemcpyAsync(hd, dbg, sizeof(hd), hipMemcpyDeviceToHost, st) != hipSuccess ||
-		   hipStreamSynchronize(st) != hipSuccess)
-			memset(hd, 0, sizeof(hd));
-		double acc[8] = {0};
-		int cnt = 0;
-		for(int s_ = 0; s_ < 1024; ++s_) {
-			const unsigned long long *t_ = hd + s_ * 8;
-			if(!t_[0] || !t_[5]) continue;
-			for(int p_ = 1; p_ < 6; ++p_) acc[p_] += (double) (t_[p_] - t_[p_ - 1]) * 10.0;
-			acc[6] += (double) t_[6];
-			++cnt;
-		}
-		if(cnt)
-			fprintf(stderr, "pick phases over %d joins (ns): entry->loads %.0f, count+scan %.0f, entries %.0f, replay %.0f, gather %.0f; total entries %.1f\n",
-			        cnt, acc[1] / cnt, acc[2] / cnt, acc[3] / cnt, acc[4] / cnt, acc[5] / cnt, acc[6] / cnt);
-		hipFree(dbg);
-	}
-	SD_HIP(hipMemcpyAsync(&hc, b.ctl, sizeof(hc), hipMemcpyDeviceToHost, st));
-	SD_HIP(hipStreamSynchronize(st));
-	SD_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-	*njoins = hc.njoins;
-	*final_n = hc.done ? hc.final_n : n;
-	if(hc.njoins) {
-		SD_HIP(hipMemcpyAsync(joins, b.joins, (size_t) hc.njoins * sizeof(ccg_join), hipMemcpyDeviceToHost, st));
-	}
-	*final_d = -1.0;
+	CCG_TRY(run.finish(hc, n, b.joins, joins, njoins, final_n, final_d));
+	if(dbg) pick_ts_report(dbg, st);
 	if(*final_n == 2) {
 		// D(1, 0): row 1 is in band 0, owned by rank 0
-		SD_TRY(cr.bcast(sh.rank == 0 ? (const void *) (D + sh.off(1)) : NULL, Xm, ET, 0));
-		T v;
-		SD_HIP(hipMemcpyAsync(&v, Xm, sizeof(T), hipMemcpyDeviceToHost, st));
-		SD_HIP(hipStreamSynchronize(st));
-		*final_d = (ET == 8 || ET == 4) ? (double) v : v / bs;
+		CCG_TRY(cr.bcast(sh.rank == 0 ? (const void *) (D + sh.off(1)) : NULL, Xm, ET, 0));
+		CCG_TRY(run.final_distance<ET>(Xm, bs, final_d));
 	}
-	if(b.lbskip) {   // the bounded-out cells, from the per-wave slots
-		std::vector<long long> sl((size_t) LB_SCAN * LB_SLOT);
-		SD_HIP(hipMemcpyAsync(sl.data(), b.lbskip, sl.size() * 8, hipMemcpyDeviceToHost, st));
-		SD_HIP(hipStreamSynchronize(st));
-		for(size_t x = 0; x < (size_t) LB_SCAN; ++x) hc.cells_lbskip += sl[x * LB_SLOT];
-	}
-	if(stats) {
-		stats[0] = hc.rows;
-		stats[1] = hc.cells - hc.cells_lbskip;   // cells the scans loaded
-		stats[2] = launches;
-		stats[3] = (int64_t) (ms * 1000.0);
-		if(a->profile) {
-			for(int c = 0; c < CCG_NKSTAT; ++c) {
-				stats[4 + 2 * c] = kt.cnt[c];
-				stats[5 + 2 * c] = kt.ns[c];
-			}
-			stats[4 + 2 * CCG_NKSTAT] = hc.cells_top;
-			stats[5 + 2 * CCG_NKSTAT] = hc.cells_rest - hc.cells_lbskip;
-			stats[6 + 2 * CCG_NKSTAT] = hc.serial_sums;
-			stats[7 + 2 * CCG_NKSTAT] = hc.chain_sums;
-			stats[8 + 2 * CCG_NKSTAT] = istat.coll_bytes;
-			stats[9 + 2 * CCG_NKSTAT] = istat.hard;
-			stats[10 + 2 * CCG_NKSTAT] = hc.ref_rows;
-			stats[11 + 2 * CCG_NKSTAT] = hc.ref_cells;
-		}
-	}
-out:
-#undef SD_TRY
-#undef SD_HIP
-	if(rc != CCG_OK && kt.on) {   // the profiled run ended early: release its events
-		for(int k = 0; k < 1025; ++k) hipEventDestroy(kt.ev[k]);
-		kt.on = false;
-	}
-	hipStreamSynchronize(st);
-	if(h) hipHostFree(h);
-	if(lbmem) hipFree(lbmem);
-	hipFree(m);
-	hipFree(w.mem);
-	return rc;
+	CCG_TRY(lb_harvest(b, LB_SCAN, st, hc));
+	TreeStats s = run.stats();
+	s.rows = hc.rows;
+	s.cells = hc.cells - hc.cells_lbskip;   // cells the scans loaded
+	s.cells_top = hc.cells_top;
+	s.cells_rest = hc.cells_rest - hc.cells_lbskip;
+	s.serial_sums = hc.serial_sums;
+	s.chain_sums = hc.chain_sums;
+	s.slot8 = istat.coll_bytes;
+	s.hard_columns = istat.hard;
+	s.ref_rows = hc.ref_rows;
+	s.ref_cells = hc.ref_cells;
+	s.write(stats, a->profile != 0, kt);
+	return run.end();
 }
 
 // called by ccg_tree_shard_dev (tree_shard.hip) for method CCG_TREE_DNJ;

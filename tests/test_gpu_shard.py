@@ -519,3 +519,31 @@ def test_shard_multiblock_plan(dev, monkeypatch, tmp_path, world, n, kind, et):
         for r in range(world):
             fn, fd = np.load(tmp_path / f"f{r}.npy")
             _same((np.load(tmp_path / f"j{r}.npy"), int(fn), fd), ref)
+
+
+def _clade_ltd(n, seed, L=3000, clades=16):
+    """test_gpu.py's clade-structured SNP distances (the same draws)"""
+    rng = np.random.default_rng(seed)
+    X = rng.integers(0, 4, (clades, L))[rng.integers(0, clades, n)]
+    X = np.where(rng.random((n, L)) < 0.01, rng.integers(0, 4, (n, L)), X)
+    same = sum((X == c).astype(np.float64) @ (X == c).astype(np.float64).T for c in range(4))
+    i, j = np.tril_indices(n, -1)
+    return L - same[i, j]
+
+
+def test_shard_plan_wait_timeout_is_an_error(dev, monkeypatch):
+    """The sharded kernels at world 1 report a timed-out look-back of their
+    multi-block k_dnj_plan as an error, as the single engine does
+    (test_dnj_plan_wait_timeout_is_an_error), never as a truncated join list:
+    CCG_TEST_WITHHOLD=1 makes block 0 withhold its entry count.  (The sharded
+    plan has no helper blocks, so the knob's bit 1 does not apply.)"""
+    from ccphylo_amd import CcgError
+    n = 3000
+    monkeypatch.setenv("CCG_PLAN_FR", "1")   # several listing blocks at this size
+    monkeypatch.setenv("CCG_S_SPLIT_N", "100")
+    D = _clade_ltd(n, 5)
+    got, fn, _, _ = dev.tree_shard(D, n, None, method=1, exact=True)   # the same settings without the knob: a tree
+    assert fn == 2 and len(got) == n - 2
+    monkeypatch.setenv("CCG_TEST_WITHHOLD", "1")
+    with pytest.raises(CcgError):
+        dev.tree_shard(D, n, None, method=1, exact=True)
