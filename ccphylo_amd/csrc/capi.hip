@@ -28,7 +28,7 @@ void ccg_set_last_msg(const char *msg) {
 	fprintf(stderr, "ccphylo_amd: %s\n", g_last_error);
 }
 
-int ccg_ctx_workspace(ccg_ctx *c, int k, size_t bytes, void **p) {
+int ccg_ctx_workspace(ccg_ctx *c, ccg_ws_slot k, size_t bytes, void **p) {
 	if(c->ws[k] && c->ws_bytes[k] >= bytes) {
 		*p = c->ws[k];
 		return CCG_OK;
@@ -159,7 +159,7 @@ void ccg_destroy(ccg_ctx *c) {
 	if(!c) return;
 	hipSetDevice(c->device);
 	if(!(c->masked && g_shut)) hipStreamSynchronize(c->stream);
-	for(int k = 0; k < 6; ++k)
+	for(int k = 0; k < CCG_WS_COUNT; ++k)
 		if(c->ws[k]) hipFree(c->ws[k]);
 	hipEventDestroy(c->ev0);
 	hipEventDestroy(c->ev1);
@@ -211,42 +211,30 @@ int ccg_snp_ltd(ccg_ctx *c, const ccg_snp_args *a, void *D, void *N, int *inc_ou
 	CCG_CHECK(hipSetDevice(c->device));
 	size_t n = (size_t) a->n;
 	size_t lt = n > 1 ? n * (n - 1) / 2 * (size_t) a->etype : 0;
-	void *d_D = NULL, *d_N = NULL;
-	int rc = CCG_OK;
-	if(hipMalloc(&d_D, lt ? lt : 8) != hipSuccess || (N && a->pair && hipMalloc(&d_N, lt ? lt : 8) != hipSuccess)) {
-		rc = CCG_ENOMEM;
-		goto done;
-	}
+	DevMem d_D, d_N;
+	CCG_TRY(d_D.alloc(lt));
+	if(N && a->pair) CCG_TRY(d_N.alloc(lt));
+	StreamSync idle(c->stream);
 	// untouched cells (outside a row range) keep the caller's contents
 	if(lt && (a->row_begin || a->row_end)) {
-		if(hipMemcpyAsync(d_D, D, lt, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-		   (d_N && hipMemcpyAsync(d_N, N, lt, hipMemcpyHostToDevice, c->stream) != hipSuccess)) {
-			rc = CCG_EHIP;
-			goto done;
-		}
+		CCG_CHECK(hipMemcpyAsync(d_D.p, D, lt, hipMemcpyHostToDevice, c->stream));
+		if(d_N.p) CCG_CHECK(hipMemcpyAsync(d_N.p, N, lt, hipMemcpyHostToDevice, c->stream));
 	}
 	// the packed sequences stream from host memory into the bit planes
-	rc = ccg_snp_dev_impl(c, a, d_D, d_N, inc_out, true);
-	if(rc == CCG_OK && lt) {
-		if(hipMemcpyAsync(D, d_D, lt, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-		   (d_N && hipMemcpyAsync(N, d_N, lt, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-		   hipStreamSynchronize(c->stream) != hipSuccess) {
-			rc = CCG_EHIP;
-		}
+	CCG_TRY(ccg_snp_dev_impl(c, a, d_D.p, d_N.p, inc_out, true));
+	if(lt) {
+		CCG_CHECK(hipMemcpyAsync(D, d_D.p, lt, hipMemcpyDeviceToHost, c->stream));
+		if(d_N.p) CCG_CHECK(hipMemcpyAsync(N, d_N.p, lt, hipMemcpyDeviceToHost, c->stream));
+		CCG_CHECK(hipStreamSynchronize(c->stream));
 	}
-done:
-	hipStreamSynchronize(c->stream);
-	if(d_D) hipFree(d_D);
-	if(d_N) hipFree(d_N);
-	return rc;
+	return CCG_OK;
 }
 
 int ccg_tree_dev(ccg_ctx *c, const ccg_tree_args *a, void *D, ccg_join *joins, int *njoins, int *final_n,
                  double *final_d, int64_t *stats) {
 	if(!c || !a || !D || !joins || !njoins || !final_n || !final_d) return CCG_EINVAL;
 	if(a->n < 3 || a->method < CCG_TREE_NJ || a->method > CCG_TREE_MN) return CCG_EINVAL;
-	if(a->etype != 8 && a->etype != 4 && a->etype != 2 && a->etype != 1) return CCG_EINVAL;
-	if((a->etype == 2 || a->etype == 1) && !(a->byteScale != 0)) return CCG_EINVAL;
+	if(!ccg_etype_ok(a->etype) || !ccg_etype_scale_ok(a->etype, a->byteScale)) return CCG_EINVAL;
 	CCG_CHECK(hipSetDevice(c->device));
 	CCG_DEVICE_SYNC(c);   // inputs may come from other streams (e.g. torch's)
 	return ccg_tree_impl(c, a, D, joins, njoins, final_n, final_d, stats, NULL, NULL);
@@ -256,8 +244,7 @@ int ccg_tree_dev_state(ccg_ctx *c, const ccg_tree_args *a, void *D, const ccg_dn
                        ccg_join *joins, int *njoins, int *final_n, double *final_d, int64_t *stats) {
 	if(!c || !a || !D || !joins || !njoins || !final_n || !final_d) return CCG_EINVAL;
 	if(a->n < 3 || a->method != CCG_TREE_DNJ) return CCG_EINVAL;
-	if(a->etype != 8 && a->etype != 4 && a->etype != 2 && a->etype != 1) return CCG_EINVAL;
-	if((a->etype == 2 || a->etype == 1) && !(a->byteScale != 0)) return CCG_EINVAL;
+	if(!ccg_etype_ok(a->etype) || !ccg_etype_scale_ok(a->etype, a->byteScale)) return CCG_EINVAL;
 	if(in && (in->n != a->n || !in->sD || !in->Q || !in->N || !in->P || in->cand < 0 || in->cand >= in->n))
 		return CCG_EINVAL;
 	if(out && (!out->sD || !out->Q || !out->N || !out->P)) return CCG_EINVAL;
@@ -270,20 +257,14 @@ int ccg_tree(ccg_ctx *c, const ccg_tree_args *a, const void *D, ccg_join *joins,
              double *final_d, int64_t *stats) {
 	if(!c || !a || !D) return CCG_EINVAL;
 	if(a->n < 3 || a->method < CCG_TREE_NJ || a->method > CCG_TREE_MN) return CCG_EINVAL;
-	if(a->etype != 8 && a->etype != 4 && a->etype != 2 && a->etype != 1) return CCG_EINVAL;
+	if(!ccg_etype_ok(a->etype)) return CCG_EINVAL;
 	CCG_CHECK(hipSetDevice(c->device));
 	size_t bytes = (size_t) a->n * (size_t) (a->n - 1) / 2 * (size_t) a->etype;
-	void *d = NULL;
-	if(hipMalloc(&d, bytes) != hipSuccess) return CCG_ENOMEM;
-	int rc = CCG_OK;
-	if(hipMemcpyAsync(d, D, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
-		rc = CCG_EHIP;
-	} else {
-		rc = ccg_tree_dev(c, a, d, joins, njoins, final_n, final_d, stats);
-	}
-	hipStreamSynchronize(c->stream);
-	hipFree(d);
-	return rc;
+	DevMem d;
+	CCG_TRY(d.alloc(bytes));
+	StreamSync idle(c->stream);
+	CCG_CHECK(hipMemcpyAsync(d.p, D, bytes, hipMemcpyHostToDevice, c->stream));
+	return ccg_tree_dev(c, a, d.p, joins, njoins, final_n, final_d, stats);
 }
 
 int ccg_malloc(ccg_ctx *c, void **p, size_t bytes) {

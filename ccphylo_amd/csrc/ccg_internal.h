@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <float.h>
+#include <type_traits>
 #include "ccphylo_amd.h"
 
 #define CCG_CHECK(expr)                                                        \
@@ -22,9 +23,30 @@
 		}                                                                      \
 	} while(0)
 
+// the same for a call that returns a CCG_* code
+#define CCG_TRY(x)                        \
+	do {                                  \
+		const int rc_ = (x);              \
+		if(rc_ != CCG_OK) return rc_;     \
+	} while(0)
+
 void ccg_set_last_error(hipError_t e, const char *what, const char *file, int line);
 // free-form text for ccg_strerror(CCG_EHIP) (collective transports)
 void ccg_set_last_msg(const char *msg);
+
+// The slots of a context's workspace cache.  Every context keeps the tree's,
+// dbscan's, the vec pre-pass's and the motif masking's slots from first use to
+// ccg_destroy; the dist's slot is used by a CCG_CTX_NOSYNC context only (any
+// other context allocates the dist's buffers per call and frees them with it).
+enum ccg_ws_slot {
+	CCG_WS_TREE,      // the tree drivers' run state (tree_layout, lk_run_t's buffers)
+	CCG_WS_TREE_LB,   // DNJ's block lower bounds (optional: a run goes without)
+	CCG_WS_DIST,      // the dist's bit planes, included count and word list (CCG_CTX_NOSYNC only)
+	CCG_WS_DBSCAN,    // dbscan's per-row vectors and counters
+	CCG_WS_VEC,       // the vec pre-pass's per-row values
+	CCG_WS_METH,      // the motif masking's counters
+	CCG_WS_COUNT
+};
 
 struct ccg_ctx {
 	int device;
@@ -39,23 +61,122 @@ struct ccg_ctx {
 	int flags;       // CCG_CTX_* (ccg_ctx_configure)
 	int masked;      // the stream was created with a CU mask (ccg_ctx_configure)
 	int ncu, cus;    // the device's CUs; the CUs the stream may use (0: all)
-	// device workspaces kept across runs (grown on demand, freed by
-	// ccg_destroy): slots 0 / 1 the tree's, slot 2 the dist's bit planes in a
-	// CCG_CTX_NOSYNC context, slot 3 dbscan's per-row vectors, slot 4 the vec
-	// pre-pass's per-row values, slot 5 the motif masking's counters.  A run then
-	// makes no hipFree, which waits for
-	// every stream of the device, so such a context never waits for another
-	void *ws[6];
-	size_t ws_bytes[6];
+	// device workspaces kept across runs (ccg_ws_slot: grown on demand, freed
+	// by ccg_destroy).  A run that uses one makes no hipFree, which waits for
+	// every stream of the device.
+	void *ws[CCG_WS_COUNT];
+	size_t ws_bytes[CCG_WS_COUNT];
 };
 // slot k of the context's workspace cache, at least `bytes` long
-int ccg_ctx_workspace(ccg_ctx *c, int k, size_t bytes, void **p);
+int ccg_ctx_workspace(ccg_ctx *c, ccg_ws_slot k, size_t bytes, void **p);
 // every device-pointer entry point first waits for the whole device (inputs
 // may come from other streams) unless the caller orders them itself
 #define CCG_DEVICE_SYNC(c) \
 	do { \
 		if(!((c)->flags & CCG_CTX_NOSYNC)) CCG_CHECK(hipDeviceSynchronize()); \
 	} while(0)
+
+// ---------------------------------------------------------------- host: owned memory
+// Device memory in host code lives in a DevMem or in a context workspace slot
+// (DESIGN.md 4).  A DevMem frees what it allocated when its scope ends, so a
+// CCG_CHECK may return from anywhere below it; what it borrows (a slot's
+// memory) it leaves alone.  p stays NULL when alloc fails.
+struct DevMem {
+	char *p = NULL;
+	bool owned = false;
+	DevMem() {}
+	DevMem(const DevMem &) = delete;
+	~DevMem() { release(); }
+	// CCG_OK or CCG_ENOMEM (quietly: the sticky HIP error is cleared); 0 bytes allocate a few
+	int alloc(size_t bytes) {
+		release();
+		if(hipMalloc((void **) &p, bytes ? bytes : 8) == hipSuccess) {
+			owned = true;
+			return CCG_OK;
+		}
+		(void) hipGetLastError();
+		p = NULL;
+		return CCG_ENOMEM;
+	}
+	void borrow(void *q) {
+		release();
+		p = (char *) q;
+	}
+	void release() {
+		if(p && owned) hipFree(p);
+		p = NULL;
+		owned = false;
+	}
+	template <class T>
+	T *as() const {
+		return (T *) p;
+	}
+};
+struct PinnedMem {
+	unsigned char *p = NULL;
+	PinnedMem() {}
+	PinnedMem(const PinnedMem &) = delete;
+	~PinnedMem() {
+		if(p) hipHostFree(p);
+	}
+	bool alloc(size_t bytes) { return hipHostMalloc((void **) &p, bytes) == hipSuccess; }
+};
+// Waits for a stream when the scope ends.  Declared after the holders a
+// function's launches use, it runs before they free: no launch of a call that
+// returns early still reads the memory (on the success paths the stream is
+// idle by then).
+struct StreamSync {
+	hipStream_t st;
+	explicit StreamSync(hipStream_t s) : st(s) {}
+	StreamSync(const StreamSync &) = delete;
+	~StreamSync() { hipStreamSynchronize(st); }
+};
+
+// Packed host rows through a bounded device stage (the dist's planes and the
+// motif masking read an MSA that may not fit beside their outputs): at most
+// CCG_STAGE_BYTES of rows a chunk, at least one row; a row is its `stride`
+// sequence words and, in pair mode, its `stride` include words, which lie
+// behind the chunk's sequences.  Per chunk: the sequences are copied, the
+// includes in pair mode, then body(sseq, sinc, t0, rows) runs (sinc NULL
+// without pair) and returns a CCG_* code.  All of it is stream-ordered, so a
+// chunk's copy waits for the previous chunk's kernels; the stage is freed
+// once the stream is idle.
+static const size_t CCG_STAGE_BYTES = (size_t) 256 << 20;
+template <class F>
+static inline int ccg_stage_rows(hipStream_t st, const uint64_t *seqs, const uint32_t *incs, long long n, int stride,
+                                 bool pair, F &&body) {
+	const size_t sb = (size_t) stride * 8, ib = (size_t) stride * 4, row_b = sb + (pair ? ib : 0);
+	long long R = (long long) (CCG_STAGE_BYTES / row_b);
+	if(R < 1) R = 1;
+	if(R > n) R = n;
+	DevMem stage;
+	CCG_TRY(stage.alloc((size_t) R * row_b));
+	StreamSync idle(st);
+	uint64_t *sseq = stage.as<uint64_t>();
+	uint32_t *sinc = pair ? (uint32_t *) (stage.p + (size_t) R * sb) : NULL;
+	for(long long t0 = 0; t0 < n; t0 += R) {
+		const long long rows = n - t0 < R ? n - t0 : R;
+		CCG_CHECK(hipMemcpyAsync(sseq, seqs + (size_t) t0 * stride, (size_t) rows * sb, hipMemcpyHostToDevice, st));
+		if(pair) CCG_CHECK(hipMemcpyAsync(sinc, incs + (size_t) t0 * stride, (size_t) rows * ib, hipMemcpyHostToDevice, st));
+		CCG_TRY(body(sseq, sinc, t0, rows));
+	}
+	return CCG_OK;
+}
+
+// ---------------------------------------------------------------- element types
+static inline bool ccg_etype_ok(int et) { return et == 8 || et == 4 || et == 2 || et == 1; }
+// the integer types divide by the byte scale
+static inline bool ccg_etype_scale_ok(int et, double byteScale) { return !(et == 2 || et == 1) || byteScale != 0; }
+// the <ET> template argument from a checked runtime value: f(std::integral_constant<int, ET>())
+template <class F>
+static inline auto with_etype(int et, F &&f) {
+	switch(et) {
+		case 8: return f(std::integral_constant<int, 8>());
+		case 4: return f(std::integral_constant<int, 4>());
+		case 2: return f(std::integral_constant<int, 2>());
+		default: return f(std::integral_constant<int, 1>());
+	}
+}
 
 // ---------------------------------------------------------------- numerics
 __device__ __forceinline__ int32_t cvt_i32_x86(double x) {

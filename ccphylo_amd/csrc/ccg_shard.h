@@ -435,23 +435,19 @@ static int sh_init_summad(const typename Elem<ET>::T *D, int n0, double bs, cons
 		// in chunks of at most K * n0 cells through a buffer of their own
 		long long K = 0;
 		if((rc = sh_init_chunk(n0, ET, cr.c->host_staged != 0, &K))) return rc;
-		typename Elem<ET>::T *Xc = NULL;
-		if(hipMalloc((void **) &Xc, (size_t) K * n0 * ET) != hipSuccess) return CCG_ENOMEM;
-		unsigned char *hh = (unsigned char *) malloc((size_t) n0);
-		int *hl = (int *) malloc((size_t) nh * sizeof(int));
-		if(!hh || !hl) {
-			free(hh);
-			free(hl);
-			hipFree(Xc);
-			return CCG_ENOMEM;
-		}
-		rc = hipMemcpy(hh, hard, (size_t) n0, hipMemcpyDeviceToHost) == hipSuccess ? CCG_OK : CCG_EHIP;
+		DevMem gather;
+		CCG_TRY(gather.alloc((size_t) K * n0 * ET));
+		StreamSync idle(st);
+		typename Elem<ET>::T *Xc = gather.as<typename Elem<ET>::T>();
+		std::vector<unsigned char> hh((size_t) n0);
+		std::vector<int> hl((size_t) nh);
+		CCG_CHECK(hipMemcpy(hh.data(), hard, (size_t) n0, hipMemcpyDeviceToHost));
 		int q = 0;
 		for(int c = 0; c < n0 && q < nh; ++c)
 			if(hh[c]) hl[q++] = c;
-		if(!rc && hipMemcpy(hlist, hl, (size_t) nh * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) rc = CCG_EHIP;
+		CCG_CHECK(hipMemcpy(hlist, hl.data(), (size_t) nh * sizeof(int), hipMemcpyHostToDevice));
 		// chunks of consecutive hard columns whose rows fit the buffer of K * n0 cells
-		for(int q0 = 0; q0 < nh && !rc;) {
+		for(int q0 = 0; q0 < nh;) {
 			const long long rows = n0 - hl[q0] - 1;
 			long long kq = rows > 0 ? (K * (long long) n0) / rows : nh;
 			if(kq < 1) kq = 1;
@@ -463,7 +459,7 @@ static int sh_init_summad(const typename Elem<ET>::T *D, int n0, double bs, cons
 				if(g > 65536) g = 65536;
 				k_sh_pack_cols<ET><<<(unsigned) g, TB, 0, st>>>(D, n0, sh, hlist + q0, Kc, Xc);
 				cr.kt->mark(CCG_K_INIT);
-				if((rc = cr.allreduce(Xc, (size_t) cells * ET))) break;
+				CCG_TRY(cr.allreduce(Xc, (size_t) cells * ET));
 				is->coll_bytes += cells * ET;
 			}
 			k_sh_init_cols<ET><<<cdiv(Kc, TB), TB, 0, st>>>(Xc, n0, bs, hlist + q0, Kc, rp, rcnt, b.sD, b.N, b.ctl);
@@ -471,11 +467,7 @@ static int sh_init_summad(const typename Elem<ET>::T *D, int n0, double bs, cons
 			*launches += 2;
 			q0 += Kc;
 		}
-		hipStreamSynchronize(st);
-		hipFree(Xc);
-		free(hh);
-		free(hl);
-		if(rc) return rc;
+		CCG_CHECK(hipStreamSynchronize(st));   // before the gather buffer goes
 		is->hard = nh;
 	}
 	TreeCtl hc;

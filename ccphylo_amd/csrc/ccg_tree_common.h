@@ -152,12 +152,12 @@ __device__ __forceinline__ unsigned lb_bits(double x) {
 }
 
 
-// the device state of one tree run (one hipMalloc), sized for n taxa
+// the device state of one tree run (one piece of memory), sized for n taxa
 struct TreeWork {
 	TreeBufs b;
 	void *mem;
 };
-int ccg_tree_alloc(TreeWork *w, int n, hipStream_t st);
+int ccg_tree_alloc(DevMem &mem, TreeWork *w, int n, hipStream_t st);   // into a holder of the caller's
 size_t ccg_tree_bytes(int n);   // what ccg_tree_alloc allocates
 // CCG_TREE_UPGMA / CCG_TREE_CF / CCG_TREE_FF on a device LT (tree_linkage.hip)
 int ccg_tree_linkage_impl(ccg_ctx *ctx, const ccg_tree_args *a, void *Dd, ccg_join *joins, int *njoins, int *final_n,

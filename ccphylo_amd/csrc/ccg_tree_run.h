@@ -1,17 +1,11 @@
 // ccg_tree_run.h -- the host frame of the four tree drivers (tree_run_t,
 // lk_run_t, tree_shard_run_t, tree_shard_dnj_run_t): the per-kernel timer,
 // the run from the seeded control block to the copied joins, the statistics
-// vector, the block lower bounds' memory and two owning holders.  Host code
-// only; each driver keeps its own per-join body (the host drivers' frame).
+// vector and the block lower bounds' memory.  Host code only; each driver
+// keeps its own per-join body (the host drivers' frame).
 #pragma once
 #include <vector>
 #include "ccg_tree_common.h"
-
-#define CCG_TRY(x)                        \
-	do {                                  \
-		const int rc_ = (x);              \
-		if(rc_ != CCG_OK) return rc_;     \
-	} while(0)
 
 // Per-kernel HIP-event timing (profile mode): one event after every launch,
 // harvested in batches.
@@ -65,32 +59,6 @@ struct KTimer {
 		harvest();
 		abort();
 	}
-};
-
-// device / pinned host memory freed with the scope (p stays NULL when alloc fails)
-struct DevMem {
-	char *p = NULL;
-	DevMem() {}
-	explicit DevMem(void *owned) : p((char *) owned) {}
-	DevMem(const DevMem &) = delete;
-	~DevMem() {
-		if(p) hipFree(p);
-	}
-	bool alloc(size_t bytes) {
-		if(hipMalloc((void **) &p, bytes) == hipSuccess) return true;
-		(void) hipGetLastError();
-		p = NULL;
-		return false;
-	}
-};
-struct PinnedMem {
-	unsigned char *p = NULL;
-	PinnedMem() {}
-	PinnedMem(const PinnedMem &) = delete;
-	~PinnedMem() {
-		if(p) hipHostFree(p);
-	}
-	bool alloc(size_t bytes) { return hipHostMalloc((void **) &p, bytes) == hipSuccess; }
 };
 
 // the seed of a run's control block

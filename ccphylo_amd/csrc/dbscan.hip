@@ -177,21 +177,16 @@ static void launch_border(ccg_ctx *c, const void *D, double bs, double maxDist, 
 
 static int dbscan_args_ok(const ccg_dbscan_args *a) {
 	if(a->n < 1) return 0;
-	if(a->etype != 8 && a->etype != 4 && a->etype != 2 && a->etype != 1) return 0;
-	if((a->etype == 2 || a->etype == 1) && !(a->byteScale != 0)) return 0;
-	return 1;
+	return ccg_etype_ok(a->etype) && ccg_etype_scale_ok(a->etype, a->byteScale);
 }
 
 // the count pass on zeroed N / DB_NONE fany
 static int dbscan_count(ccg_ctx *c, const ccg_dbscan_args *a, const void *D, int *N, int *fany) {
 	CCG_CHECK(hipMemsetAsync(N, 0, (size_t) a->n * sizeof(int), c->stream));
 	CCG_CHECK(hipMemsetAsync(fany, 0x7f, (size_t) a->n * sizeof(int), c->stream));
-	switch(a->etype) {
-		case 8: launch_count<8>(c, D, a->n, a->byteScale, a->maxDist, N, fany); break;
-		case 4: launch_count<4>(c, D, a->n, a->byteScale, a->maxDist, N, fany); break;
-		case 2: launch_count<2>(c, D, a->n, a->byteScale, a->maxDist, N, fany); break;
-		default: launch_count<1>(c, D, a->n, a->byteScale, a->maxDist, N, fany); break;
-	}
+	with_etype(a->etype, [&](auto et) {
+		launch_count<decltype(et)::value>(c, D, a->n, a->byteScale, a->maxDist, N, fany);
+	});
 	CCG_CHECK(hipGetLastError());
 	return CCG_OK;
 }
@@ -220,7 +215,7 @@ extern "C" int ccg_dbscan_dev(ccg_ctx *c, const ccg_dbscan_args *a, const void *
 	// workspace: N, fany, f, f', border list (n ints each), then the counters
 	void *ws = NULL;
 	const size_t nn = ((size_t) n + 3) & ~(size_t) 3;
-	int rc = ccg_ctx_workspace(c, 3, (5 * nn + 8) * sizeof(int), &ws);
+	int rc = ccg_ctx_workspace(c, CCG_WS_DBSCAN, (5 * nn + 8) * sizeof(int), &ws);
 	if(rc) return rc;
 	int *dN = (int *) ws, *dfany = dN + nn, *df0 = dfany + nn, *df1 = df0 + nn, *dlist = df1 + nn;
 	int *dcnt = dlist + nn;   // [0] border rows, [1] changed, [2] roots, [4..5] the border pass's cells (u64)
@@ -238,12 +233,9 @@ extern "C" int ccg_dbscan_dev(ccg_ctx *c, const ccg_dbscan_args *a, const void *
 	CCG_CHECK(hipMemcpyAsync(N, dN, (size_t) n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
 	CCG_CHECK(hipStreamSynchronize(c->stream));
 	if(nborder > 0) {   // never at minN <= 1: the LT is then read exactly once
-		switch(a->etype) {
-			case 8: launch_border<8>(c, D, a->byteScale, a->maxDist, a->minN, dN, dlist, nborder, df0, dcells); break;
-			case 4: launch_border<4>(c, D, a->byteScale, a->maxDist, a->minN, dN, dlist, nborder, df0, dcells); break;
-			case 2: launch_border<2>(c, D, a->byteScale, a->maxDist, a->minN, dN, dlist, nborder, df0, dcells); break;
-			default: launch_border<1>(c, D, a->byteScale, a->maxDist, a->minN, dN, dlist, nborder, df0, dcells); break;
-		}
+		with_etype(a->etype, [&](auto et) {
+			launch_border<decltype(et)::value>(c, D, a->byteScale, a->maxDist, a->minN, dN, dlist, nborder, df0, dcells);
+		});
 		CCG_CHECK(hipGetLastError());
 		++launches;
 	}
@@ -289,15 +281,9 @@ extern "C" int ccg_dbscan(ccg_ctx *c, const ccg_dbscan_args *a, const void *D, i
 	if(a->n == 1) return ccg_dbscan_dev(c, a, NULL, N, C, nclust, stats);
 	CCG_CHECK(hipSetDevice(c->device));
 	const size_t bytes = (size_t) a->n * (size_t) (a->n - 1) / 2 * (size_t) a->etype;
-	void *d = NULL;
-	if(hipMalloc(&d, bytes) != hipSuccess) return CCG_ENOMEM;
-	int rc;
-	if(hipMemcpyAsync(d, D, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
-		rc = CCG_EHIP;
-	} else {
-		rc = ccg_dbscan_dev(c, a, d, N, C, nclust, stats);
-	}
-	hipStreamSynchronize(c->stream);
-	hipFree(d);
-	return rc;
+	DevMem d;
+	CCG_TRY(d.alloc(bytes));
+	StreamSync idle(c->stream);
+	CCG_CHECK(hipMemcpyAsync(d.p, D, bytes, hipMemcpyHostToDevice, c->stream));
+	return ccg_dbscan_dev(c, a, d.p, N, C, nclust, stats);
 }

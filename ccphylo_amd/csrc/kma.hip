@@ -375,12 +375,10 @@ __global__ __launch_bounds__(KTB) void k_kma_pairs(KmaDev a, typename Elem<ET>::
 // ------------------------------------------------------------------ host
 template <int M>
 static void launch_et(int et, unsigned grid, hipStream_t st, const KmaDev &k, void *D, void *N) {
-	switch(et) {
-		case 8: k_kma_pairs<M, 8><<<grid, KTB, 0, st>>>(k, (double *) D, (double *) N); break;
-		case 4: k_kma_pairs<M, 4><<<grid, KTB, 0, st>>>(k, (float *) D, (float *) N); break;
-		case 2: k_kma_pairs<M, 2><<<grid, KTB, 0, st>>>(k, (uint16_t *) D, (uint16_t *) N); break;
-		default: k_kma_pairs<M, 1><<<grid, KTB, 0, st>>>(k, (uint8_t *) D, (uint8_t *) N); break;
-	}
+	with_etype(et, [&](auto e) {
+		typedef typename Elem<decltype(e)::value>::T T;
+		k_kma_pairs<M, decltype(e)::value><<<grid, KTB, 0, st>>>(k, (T *) D, (T *) N);
+	});
 }
 
 static int kma_launch(int metric, int et, unsigned grid, hipStream_t st, const KmaDev &k, void *D, void *N) {
@@ -412,8 +410,7 @@ static bool kma_metric_ok(int m) {
 
 static int kma_check(const ccg_kma_args *a) {
 	if(!a || a->n < 0 || a->stride1 < 0 || a->stride2 < 0) return CCG_EINVAL;
-	if(a->etype != 8 && a->etype != 4 && a->etype != 2 && a->etype != 1) return CCG_EINVAL;
-	if((a->etype == 2 || a->etype == 1) && !(a->byteScale != 0)) return CCG_EINVAL;
+	if(!ccg_etype_ok(a->etype) || !ccg_etype_scale_ok(a->etype, a->byteScale)) return CCG_EINVAL;
 	if(!kma_metric_ok(a->metric)) return CCG_EUNSUP;
 	if((a->metric == CCG_KMA_LN || a->metric == CCG_KMA_NLN) && a->lnorm == 0) return CCG_EINVAL;
 	return CCG_OK;
@@ -426,56 +423,46 @@ static int kma_run(ccg_ctx *c, const ccg_kma_args *a, void *D, void *N, int64_t 
 	if(fatal) *fatal = -1;
 	if(n < 2) return CCG_OK;
 	const long long rows1 = (long long) n * a->stride1, rows2 = (long long) n * a->stride2;
-	double *s = NULL;
-	unsigned long long *fat = NULL;
-	int rc = CCG_OK;
 	const bool cos = a->metric == CCG_KMA_COS;
-	if(hipMalloc((void **) &fat, 8 + (size_t) n * 4) != hipSuccess ||
-	   (cos && hipMalloc((void **) &s, (size_t) (rows1 + rows2 + 1) * 8) != hipSuccess)) {
-		rc = CCG_ENOMEM;
-	} else {
-		KmaDev k;
-		k.rec1 = (const uint4 *) a->rec1;
-		k.rec2 = (const uint4 *) a->rec2;
-		k.s1 = s;
-		k.s2 = s ? s + rows1 : NULL;
-		k.len1 = a->len1;
-		k.len2 = a->len2;
-		k.stride1 = a->stride1;
-		k.stride2 = a->stride2;
-		k.n = n;
-		k.minDepth = a->minDepth;
-		k.minLength = a->minLength;
-		k.norm = a->norm;
-		k.ln = a->lnorm;
-		k.minCov = a->minCov;
-		k.bs = a->byteScale;
-		k.fatal = fat;
-		k.nnucs = (const unsigned *) (fat + 1);
-		unsigned long long none = ~0ull;
-		if(hipMemcpyAsync(fat, &none, 8, hipMemcpyHostToDevice, st) != hipSuccess) rc = CCG_EHIP;
-		if(!rc) k_kma_nnucs<<<n, 256, 0, st>>>(k.rec2, a->len2, a->stride2, a->minDepth, (unsigned *) (fat + 1));
-		if(!rc && cos) {
-			k_kma_norms<<<2048, 256, 0, st>>>(k.rec1, rows1, s);
-			k_kma_norms<<<2048, 256, 0, st>>>(k.rec2, rows2, s + rows1);
-		}
-		const long long nb = (n + KT - 1) / KT, tiles = nb * (nb + 1) / 2;
-		if(!rc) rc = kma_launch(a->metric, a->etype, (unsigned) tiles, st, k, D, N);
-		if(!rc && hipGetLastError() != hipSuccess) rc = CCG_EHIP;
-		if(!rc) {
-			unsigned long long h = 0;
-			if(hipMemcpyAsync(&h, fat, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-			   hipStreamSynchronize(st) != hipSuccess) {
-				rc = CCG_EHIP;
-			} else if(fatal) {
-				*fatal = h == ~0ull ? -1 : (int64_t) h;
-			}
-		}
+	DevMem fatm, norms;   // the fatal index and nNucs per sample; cos: the row norms
+	CCG_TRY(fatm.alloc(8 + (size_t) n * 4));
+	if(cos) CCG_TRY(norms.alloc((size_t) (rows1 + rows2 + 1) * 8));
+	StreamSync idle(st);
+	unsigned long long *fat = fatm.as<unsigned long long>();
+	double *s = norms.as<double>();
+	KmaDev k;
+	k.rec1 = (const uint4 *) a->rec1;
+	k.rec2 = (const uint4 *) a->rec2;
+	k.s1 = s;
+	k.s2 = s ? s + rows1 : NULL;
+	k.len1 = a->len1;
+	k.len2 = a->len2;
+	k.stride1 = a->stride1;
+	k.stride2 = a->stride2;
+	k.n = n;
+	k.minDepth = a->minDepth;
+	k.minLength = a->minLength;
+	k.norm = a->norm;
+	k.ln = a->lnorm;
+	k.minCov = a->minCov;
+	k.bs = a->byteScale;
+	k.fatal = fat;
+	k.nnucs = (const unsigned *) (fat + 1);
+	unsigned long long none = ~0ull;
+	CCG_CHECK(hipMemcpyAsync(fat, &none, 8, hipMemcpyHostToDevice, st));
+	k_kma_nnucs<<<n, 256, 0, st>>>(k.rec2, a->len2, a->stride2, a->minDepth, (unsigned *) (fat + 1));
+	if(cos) {
+		k_kma_norms<<<2048, 256, 0, st>>>(k.rec1, rows1, s);
+		k_kma_norms<<<2048, 256, 0, st>>>(k.rec2, rows2, s + rows1);
 	}
-	hipStreamSynchronize(st);
-	if(s) hipFree(s);
-	if(fat) hipFree(fat);
-	return rc;
+	const long long nb = (n + KT - 1) / KT, tiles = nb * (nb + 1) / 2;
+	CCG_TRY(kma_launch(a->metric, a->etype, (unsigned) tiles, st, k, D, N));
+	CCG_CHECK(hipGetLastError());
+	unsigned long long h = 0;
+	CCG_CHECK(hipMemcpyAsync(&h, fat, 8, hipMemcpyDeviceToHost, st));
+	CCG_CHECK(hipStreamSynchronize(st));
+	if(fatal) *fatal = h == ~0ull ? -1 : (int64_t) h;
+	return CCG_OK;
 }
 
 extern "C" {
@@ -498,11 +485,12 @@ int ccg_kma_ltd(ccg_ctx *c, const ccg_kma_args *a, void *D, void *N, int64_t *fa
 	CCG_CHECK(hipSetDevice(c->device));
 	const size_t n = (size_t) a->n, b1 = n * (size_t) a->stride1 * 16, b2 = n * (size_t) a->stride2 * 16;
 	const size_t lt = n * (n - 1) / 2 * (size_t) a->etype;
-	char *m = NULL;
-	const size_t sz = b1 + b2 + 2 * n * 4 + 2 * lt + 64;
-	if(hipMalloc((void **) &m, sz) != hipSuccess) return CCG_ENOMEM;
+	DevMem mem;
+	CCG_TRY(mem.alloc(b1 + b2 + 2 * n * 4 + 2 * lt + 64));
+	hipStream_t st = c->stream;
+	StreamSync idle(st);
 	ccg_kma_args d = *a;
-	char *p = m;
+	char *p = mem.p;
 	d.rec1 = (const uint16_t *) p;
 	p += (b1 + 15) & ~(size_t) 15;
 	d.rec2 = (const uint16_t *) p;
@@ -513,23 +501,15 @@ int ccg_kma_ltd(ccg_ctx *c, const ccg_kma_args *a, void *D, void *N, int64_t *fa
 	p += n * 4;
 	p = (char *) (((uintptr_t) p + 15) & ~(uintptr_t) 15);
 	void *dD = p, *dN = N ? p + lt : NULL;
-	hipStream_t st = c->stream;
-	if(hipMemcpyAsync((void *) d.rec1, a->rec1, b1, hipMemcpyHostToDevice, st) != hipSuccess ||
-	   hipMemcpyAsync((void *) d.rec2, a->rec2, b2, hipMemcpyHostToDevice, st) != hipSuccess ||
-	   hipMemcpyAsync((void *) d.len1, a->len1, n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
-	   hipMemcpyAsync((void *) d.len2, a->len2, n * 4, hipMemcpyHostToDevice, st) != hipSuccess) {
-		rc = CCG_EHIP;
-	} else {
-		rc = kma_run(c, &d, dD, dN, fatal);
-	}
-	if(!rc && (hipMemcpyAsync(D, dD, lt, hipMemcpyDeviceToHost, st) != hipSuccess ||
-	           (N && hipMemcpyAsync(N, dN, lt, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-	           hipStreamSynchronize(st) != hipSuccess)) {
-		rc = CCG_EHIP;
-	}
-	hipStreamSynchronize(st);
-	hipFree(m);
-	return rc;
+	CCG_CHECK(hipMemcpyAsync((void *) d.rec1, a->rec1, b1, hipMemcpyHostToDevice, st));
+	CCG_CHECK(hipMemcpyAsync((void *) d.rec2, a->rec2, b2, hipMemcpyHostToDevice, st));
+	CCG_CHECK(hipMemcpyAsync((void *) d.len1, a->len1, n * 4, hipMemcpyHostToDevice, st));
+	CCG_CHECK(hipMemcpyAsync((void *) d.len2, a->len2, n * 4, hipMemcpyHostToDevice, st));
+	CCG_TRY(kma_run(c, &d, dD, dN, fatal));
+	CCG_CHECK(hipMemcpyAsync(D, dD, lt, hipMemcpyDeviceToHost, st));
+	if(N) CCG_CHECK(hipMemcpyAsync(N, dN, lt, hipMemcpyDeviceToHost, st));
+	CCG_CHECK(hipStreamSynchronize(st));
+	return CCG_OK;
 }
 
 }   // extern "C"

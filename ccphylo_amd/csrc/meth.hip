@@ -150,11 +150,11 @@ static int meth_launch(ccg_ctx *c, const ccg_meth_args *a, const uint64_t *seqs,
 	return CCG_OK;
 }
 
-// slot 5 of the context's workspaces: n getNpos counts, then the match counter
+// the context's CCG_WS_METH slot: n getNpos counts, then the match counter
 static int meth_counters(ccg_ctx *c, int n, int32_t **cnt, unsigned long long **mt) {
 	void *p = NULL;
 	const size_t cb = ((size_t) n * 4 + 7) & ~(size_t) 7;
-	const int rc = ccg_ctx_workspace(c, 5, cb + 8, &p);
+	const int rc = ccg_ctx_workspace(c, CCG_WS_METH, cb + 8, &p);
 	if(rc) return rc;
 	*cnt = (int32_t *) p;
 	*mt = (unsigned long long *) ((char *) p + cb);
@@ -208,54 +208,37 @@ int ccg_meth_mask(ccg_ctx *c, const ccg_meth_args *a, int32_t *inc_count, int64_
 	if(matches) *matches = 0;
 	if(a->n == 0 || a->nmotifs == 0) return CCG_OK;
 	CCG_CHECK(hipSetDevice(c->device));
-	// the rows stream through a bounded staging buffer, as ccg_snp_ltd's do
-	const size_t sb = (size_t) a->stride * 8, ib = (size_t) a->stride * 4, row_b = sb + (a->pair ? ib : 0);
-	long long R = (long long) (((size_t) 256 << 20) / row_b);
-	if(R < 1) R = 1;
-	if(R > a->n) R = a->n;
+	const size_t ib = (size_t) a->stride * 4;
 	const int Wd = (a->len + 31) / 32;
 	int32_t *cnt = NULL;
 	unsigned long long *mt = NULL;
 	if((rc = meth_counters(c, a->n, &cnt, &mt))) return rc;
-	void *stage = NULL;
-	uint32_t *mask = NULL;
-	CCG_CHECK(hipMalloc(&stage, (size_t) R * row_b));
-	uint64_t *sseq = (uint64_t *) stage;
-	uint32_t *sinc = (uint32_t *) ((char *) stage + (size_t) R * sb);
+	DevMem maskm;   // non-pair: the one global mask, read back after the last chunk
+	StreamSync idle(c->stream);
 	if(!a->pair) {
-		if(hipMalloc((void **) &mask, ib) != hipSuccess) rc = CCG_ENOMEM;
-		else if(hipMemcpyAsync(mask, a->incs, ib, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = CCG_EHIP;
+		CCG_TRY(maskm.alloc(ib));
+		CCG_CHECK(hipMemcpyAsync(maskm.p, a->incs, ib, hipMemcpyHostToDevice, c->stream));
 	}
-	for(long long t0 = 0; t0 < a->n && rc == CCG_OK; t0 += R) {
-		const int rows = (int) (a->n - t0 < R ? a->n - t0 : R);
-		// stream-ordered: the copy into the stage waits for the previous chunk's kernels and read-back
-		if(hipMemcpyAsync(sseq, a->seqs + (size_t) t0 * a->stride, (size_t) rows * sb, hipMemcpyHostToDevice,
-		                  c->stream) != hipSuccess ||
-		   (a->pair && hipMemcpyAsync(sinc, a->incs + (size_t) t0 * a->stride, (size_t) rows * ib,
-		                              hipMemcpyHostToDevice, c->stream) != hipSuccess)) {
-			rc = CCG_EHIP;
-			break;
-		}
-		if((rc = meth_launch(c, a, sseq, a->pair ? sinc : mask, rows, matches ? mt : NULL))) break;
-		if(a->pair) {
-			if(inc_count) k_meth_npos<<<rows < 65536 ? rows : 65536, 256, 0, c->stream>>>(sinc, rows, a->stride, Wd, cnt + t0);
-			if(hipGetLastError() != hipSuccess ||
-			   hipMemcpyAsync(a->incs + (size_t) t0 * a->stride, sinc, (size_t) rows * ib, hipMemcpyDeviceToHost,
-			                  c->stream) != hipSuccess)
-				rc = CCG_EHIP;
-		}
-	}
-	if(rc == CCG_OK && !a->pair) {
+	uint32_t *mask = maskm.as<uint32_t>();
+	// the rows stream through a bounded staging buffer, as ccg_snp_ltd's do
+	// (the copy into the stage waits for the previous chunk's kernels and read-back)
+	CCG_TRY(ccg_stage_rows(c->stream, a->seqs, a->incs, a->n, a->stride, a->pair != 0,
+	                       [&](uint64_t *sseq, uint32_t *sinc, long long t0, long long rows) {
+		CCG_TRY(meth_launch(c, a, sseq, a->pair ? sinc : mask, (int) rows, matches ? mt : NULL));
+		if(!a->pair) return CCG_OK;
+		if(inc_count)
+			k_meth_npos<<<rows < 65536 ? (int) rows : 65536, 256, 0, c->stream>>>(sinc, (int) rows, a->stride, Wd, cnt + t0);
+		CCG_CHECK(hipGetLastError());
+		CCG_CHECK(hipMemcpyAsync(a->incs + (size_t) t0 * a->stride, sinc, (size_t) rows * ib, hipMemcpyDeviceToHost,
+		                         c->stream));
+		return CCG_OK;
+	}));
+	if(!a->pair) {
 		if(inc_count) k_meth_npos<<<1, 256, 0, c->stream>>>(mask, 1, a->stride, Wd, cnt);
-		if(hipGetLastError() != hipSuccess ||
-		   hipMemcpyAsync(a->incs, mask, ib, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
-			rc = CCG_EHIP;
+		CCG_CHECK(hipGetLastError());
+		CCG_CHECK(hipMemcpyAsync(a->incs, mask, ib, hipMemcpyDeviceToHost, c->stream));
 	}
-	if(rc == CCG_OK) rc = meth_results(c, a, cnt, mt, inc_count, matches);
-	hipStreamSynchronize(c->stream);
-	hipFree(stage);
-	if(mask) hipFree(mask);
-	return rc;
+	return meth_results(c, a, cnt, mt, inc_count, matches);
 }
 
 }   // extern "C"

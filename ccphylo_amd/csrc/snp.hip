@@ -1699,13 +1699,12 @@ static inline long long cdivll(long long a, long long b) { return (a + b - 1) / 
 // as npanels panels of `tile` owned rows, each against the column tiles below
 // its last row (those with a cell j < i); pfx prefix-sums the tiles per panel,
 // so that a launch spans many panels and fills the chip (band_ij finds a tile
-// in its device copy d_pfx, which the launcher frees).  A rank that owns no
-// row has no panel.
+// in its device copy d_pfx).  A rank that owns no row has no panel.
 struct TileRange {
 	long long t_begin = 0, t_end = 0, f0 = 0, f1 = 0;
 	int npanels = 0;
 	std::vector<long long> pfx;   // lives until the launcher has synchronised the copy
-	long long *d_pfx = NULL;
+	DevMem d_pfx;
 };
 
 static int tile_range(ccg_ctx *ctx, long long n, long long rb, long long re, int rank, int world, int tile,
@@ -1733,12 +1732,8 @@ static int tile_range(ccg_ctx *ctx, long long n, long long rb, long long re, int
 		tr->pfx[I + 1] = tr->pfx[I] + cdivll(sh.global_row(Lmax), tile);
 	}
 	const size_t pb = (size_t) (np + 1) * sizeof(long long);
-	CCG_CHECK(hipMalloc(&tr->d_pfx, pb));
-	if(hipMemcpyAsync(tr->d_pfx, tr->pfx.data(), pb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-		hipFree(tr->d_pfx);
-		tr->d_pfx = NULL;
-		return CCG_EHIP;
-	}
+	CCG_TRY(tr->d_pfx.alloc(pb));
+	CCG_CHECK(hipMemcpyAsync(tr->d_pfx.p, tr->pfx.data(), pb, hipMemcpyHostToDevice, ctx->stream));
 	tr->npanels = np;
 	tr->t_end = tr->pfx[np];
 	tr->f1 = ccg_shard_elems(n, rank, world);
@@ -1788,12 +1783,10 @@ static void with_split_band(bool split, bool band, F &&f) {
 }
 
 // the zeroed u32 split-K counts of a launcher (pair mode: dist counts, then n counts)
-static int alloc_counts(ccg_ctx *ctx, size_t elems, unsigned **cnt) {
-	if(hipMalloc(cnt, elems * sizeof(unsigned)) != hipSuccess) {
-		*cnt = NULL;
-		return CCG_ENOMEM;
-	}
-	return hipMemsetAsync(*cnt, 0, elems * sizeof(unsigned), ctx->stream) == hipSuccess ? CCG_OK : CCG_EHIP;
+static int alloc_counts(ccg_ctx *ctx, size_t elems, DevMem &cnt) {
+	CCG_TRY(cnt.alloc(elems * sizeof(unsigned)));
+	CCG_CHECK(hipMemsetAsync(cnt.p, 0, elems * sizeof(unsigned), ctx->stream));
+	return CCG_OK;
 }
 
 // the split-K epilogue over the elements [f0, f1) (fsacmpthrd.c:247-255, resp. A7)
@@ -1808,17 +1801,6 @@ static hipError_t launch_finish(ccg_ctx *ctx, const ccg_snp_args *a, const unsig
 	else k_snp_finish<ET><<<grid, 256, 0, ctx->stream>>>(cnt, f0, f0, f1, nFactor, a->byteScale, D);
 	return hipGetLastError();
 }
-
-// a launcher's one exit: after an error no launch may still read cnt / d_pfx
-static int launch_exit(ccg_ctx *ctx, int rc, unsigned *cnt, long long *d_pfx) {
-	if(rc != CCG_OK) hipStreamSynchronize(ctx->stream);
-	if(cnt && hipFree(cnt) != hipSuccess && rc == CCG_OK) rc = CCG_EHIP;
-	if(d_pfx && hipFree(d_pfx) != hipSuccess && rc == CCG_OK) rc = CCG_EHIP;
-	return rc;
-}
-
-// every failure after a launcher's first allocation leaves through its `out`
-#define SNP_TRY(x) do { if((x) != hipSuccess) { rc = CCG_EHIP; goto out; } } while(0)
 
 // k_snp_mfma3 / k_snp_mfma2 / k_snp_mfma2_pair over the LT rows [rb, re)
 // (world == 0) or over one rank's rows of the band layout (world > 0, rb = 0,
@@ -1850,22 +1832,27 @@ static int snp_launch_mfma2(ccg_ctx *ctx, const ccg_snp_args *a, const void *pla
 	const int S = plan.S, Wk = plan.Wk;
 	const long long batch = 1 << 16;
 	T *Nn = world > 0 ? NULL : (T *) N;
-	unsigned *cnt = NULL;
-	int rc = CCG_OK;
+	DevMem counts;   // (with tr.d_pfx and the stamps: freed once `idle` below has waited for the launches)
 #ifdef CCG_DIST_STAMPS
 	// the stamp sums of k_snp_mfma3, appended to the file CCG_DIST_STAMPS_OUT names (tools/dist_stamps.py reads it)
-	unsigned long long *d_st = NULL;
+	DevMem stamps;
+#endif
+	StreamSync idle(ctx->stream);
+#ifdef CCG_DIST_STAMPS
 	const char *sto = getenv("CCG_DIST_STAMPS_OUT");
 	const size_t stn = (size_t) (t_end - t_begin) * S * 2 * ST3_SLOTS;
 	const long long st_item0 = t_begin * S;
 	if(glds && sto) {
-		SNP_TRY(hipMalloc(&d_st, stn * sizeof(unsigned long long)));
-		SNP_TRY(hipMemsetAsync(d_st, 0, stn * sizeof(unsigned long long), ctx->stream));
+		CCG_TRY(stamps.alloc(stn * sizeof(unsigned long long)));
+		CCG_CHECK(hipMemsetAsync(stamps.p, 0, stn * sizeof(unsigned long long), ctx->stream));
 	}
-	SNP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(ccg_dist_stamp_buf), &d_st, sizeof(d_st)));
-	SNP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(ccg_dist_stamp_item0), &st_item0, sizeof(st_item0)));
+	unsigned long long *const d_st = stamps.as<unsigned long long>();
+	CCG_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(ccg_dist_stamp_buf), &d_st, sizeof(d_st)));
+	CCG_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(ccg_dist_stamp_item0), &st_item0, sizeof(st_item0)));
 #endif
-	if(S > 1 && (rc = alloc_counts(ctx, (size_t) (f1 - f0) * (PAIR ? 2 : 1), &cnt)) != CCG_OK) goto out;
+	if(S > 1) CCG_TRY(alloc_counts(ctx, (size_t) (f1 - f0) * (PAIR ? 2 : 1), counts));
+	unsigned *const cnt = counts.as<unsigned>();
+	const long long *const d_pfx = tr.d_pfx.as<long long>();
 	for(long long t = t_begin * S; t < t_end * S; t += batch) {
 		const long long items = t_end * S - t < batch ? t_end * S - t : batch;
 		with_split_band(S > 1, world > 0, [&](auto SP, auto BD) {
@@ -1874,28 +1861,28 @@ static int snp_launch_mfma2(ccg_ctx *ctx, const ccg_snp_args *a, const void *pla
 			if(PAIR)
 				k_snp_mfma2_pair<ET, sp, bd><<<(unsigned) items, 256, 0, ctx->stream>>>(
 				    (const uint4 *) planes, Wp, (int) n, t, items, S, Wk, a->norm, a->minLength, a->byteScale, (T *) D, Nn,
-				    rb, re, cnt, cnt ? cnt + (f1 - f0) : NULL, f0, tr.d_pfx, tr.npanels, rank, world);
+				    rb, re, cnt, cnt ? cnt + (f1 - f0) : NULL, f0, d_pfx, tr.npanels, rank, world);
 			else if(glds)   // KC3-word chunks, LDS-DMA staged
 				k_snp_mfma3<ET, sp, bd><<<(unsigned) items, 256, 0, ctx->stream>>>(
-				    pl, Wp, (int) n, t, items, S, Wk, nFactor, a->byteScale, (T *) D, rb, re, cnt, f0, tr.d_pfx, tr.npanels,
+				    pl, Wp, (int) n, t, items, S, Wk, nFactor, a->byteScale, (T *) D, rb, re, cnt, f0, d_pfx, tr.npanels,
 				    rank, world, sorder);
 			else if(kc == KC2L)
 				k_snp_mfma2<ET, sp, bd, KC2L><<<(unsigned) items, 256, 0, ctx->stream>>>(
-				    pl, Wp, (int) n, t, items, S, Wk, nFactor, a->byteScale, (T *) D, rb, re, cnt, f0, tr.d_pfx, tr.npanels,
+				    pl, Wp, (int) n, t, items, S, Wk, nFactor, a->byteScale, (T *) D, rb, re, cnt, f0, d_pfx, tr.npanels,
 				    rank, world, sorder);
 			else
 				k_snp_mfma2<ET, sp, bd, KC2><<<(unsigned) items, 256, 0, ctx->stream>>>(
-				    pl, Wp, (int) n, t, items, S, Wk, nFactor, a->byteScale, (T *) D, rb, re, cnt, f0, tr.d_pfx, tr.npanels,
+				    pl, Wp, (int) n, t, items, S, Wk, nFactor, a->byteScale, (T *) D, rb, re, cnt, f0, d_pfx, tr.npanels,
 				    rank, world, sorder);
 		});
-		SNP_TRY(hipGetLastError());
+		CCG_CHECK(hipGetLastError());
 	}
-	if(S > 1) SNP_TRY(launch_finish<ET>(ctx, a, cnt, f0, f1, nFactor, (T *) D, Nn));
-	SNP_TRY(hipStreamSynchronize(ctx->stream));
+	if(S > 1) CCG_CHECK(launch_finish<ET>(ctx, a, cnt, f0, f1, nFactor, (T *) D, Nn));
+	CCG_CHECK(hipStreamSynchronize(ctx->stream));
 #ifdef CCG_DIST_STAMPS
 	if(d_st) {
 		std::vector<unsigned long long> hs(stn);
-		SNP_TRY(hipMemcpy(hs.data(), d_st, stn * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+		CCG_CHECK(hipMemcpy(hs.data(), d_st, stn * sizeof(unsigned long long), hipMemcpyDeviceToHost));
 		FILE *sf = fopen(sto, "ab");
 		if(sf) {
 			fwrite(hs.data(), sizeof(unsigned long long), stn, sf);
@@ -1903,11 +1890,7 @@ static int snp_launch_mfma2(ccg_ctx *ctx, const ccg_snp_args *a, const void *pla
 		}
 	}
 #endif
-out:
-#ifdef CCG_DIST_STAMPS
-	if(d_st) hipFree(d_st);
-#endif
-	return launch_exit(ctx, rc, cnt, tr.d_pfx);
+	return CCG_OK;
 }
 
 // The 128 x 128 tile kernels, in snp_launch_mfma2's shape: k_snp_mfma /
@@ -1934,9 +1917,11 @@ static int snp_launch_tile128(ccg_ctx *ctx, const ccg_snp_args *a, const void *p
 	if(pair && Wk >= MFMA_KMAX) mfma = false;
 	const long long batch = world > 0 ? 1 << 16 : 1 << 14;
 	T *Nn = world > 0 ? NULL : (T *) N;
-	unsigned *cnt = NULL;
-	int rc = CCG_OK;
-	if(S > 1 && (rc = alloc_counts(ctx, (size_t) (f1 - f0) * (pair ? 2 : 1), &cnt)) != CCG_OK) goto out;
+	DevMem counts;   // (with tr.d_pfx: freed once `idle` has waited for the launches)
+	StreamSync idle(ctx->stream);
+	if(S > 1) CCG_TRY(alloc_counts(ctx, (size_t) (f1 - f0) * (pair ? 2 : 1), counts));
+	unsigned *const cnt = counts.as<unsigned>();
+	const long long *const d_pfx = tr.d_pfx.as<long long>();
 	for(long long t = tr.t_begin * S; t < tr.t_end * S; t += batch) {
 		const long long items = tr.t_end * S - t < batch ? tr.t_end * S - t : batch;
 		with_split_band(S > 1, world > 0, [&](auto SP, auto BD) {
@@ -1947,28 +1932,26 @@ static int snp_launch_tile128(ccg_ctx *ctx, const ccg_snp_args *a, const void *p
 			if(pair && mfma)
 				k_snp_mfma_pair<ET, sp, bd><<<(unsigned) items, 256, 0, ctx->stream>>>(
 				    pp, Wp, (int) n, t, items, S, Wk, a->norm, a->minLength, a->byteScale, (T *) D, Nn, rb, re, cnt, cn, f0,
-				    tr.d_pfx, tr.npanels, rank, world);
+				    d_pfx, tr.npanels, rank, world);
 			else if(pair)
 				k_snp_tile_pair<ET, sp, bd><<<(unsigned) items, 256, 0, ctx->stream>>>(
 				    pp, Wp, (int) n, t, items, S, Wk, a->norm, a->minLength, a->byteScale, (T *) D, Nn, rb, re, cnt, cn, f0,
-				    tr.d_pfx, tr.npanels, rank, world);
+				    d_pfx, tr.npanels, rank, world);
 			else if(mfma)
 				k_snp_mfma<ET, sp, bd><<<(unsigned) items, 256, 0, ctx->stream>>>(
-				    pl, Wp, (int) n, t, items, S, Wk, nFactor, a->byteScale, (T *) D, rb, re, cnt, f0, tr.d_pfx, tr.npanels,
+				    pl, Wp, (int) n, t, items, S, Wk, nFactor, a->byteScale, (T *) D, rb, re, cnt, f0, d_pfx, tr.npanels,
 				    rank, world);
 			else
 				k_snp_tile<ET, sp, bd><<<(unsigned) items, 256, 0, ctx->stream>>>(
-				    pl, Wp, (int) n, t, items, S, Wk, nFactor, a->byteScale, (T *) D, rb, re, cnt, f0, tr.d_pfx, tr.npanels,
+				    pl, Wp, (int) n, t, items, S, Wk, nFactor, a->byteScale, (T *) D, rb, re, cnt, f0, d_pfx, tr.npanels,
 				    rank, world);
 		});
-		SNP_TRY(hipGetLastError());
+		CCG_CHECK(hipGetLastError());
 	}
-	if(S > 1) SNP_TRY(launch_finish<ET>(ctx, a, cnt, f0, f1, nFactor, (T *) D, Nn));
-	SNP_TRY(hipStreamSynchronize(ctx->stream));
-out:
-	return launch_exit(ctx, rc, cnt, tr.d_pfx);
+	if(S > 1) CCG_CHECK(launch_finish<ET>(ctx, a, cnt, f0, f1, nFactor, (T *) D, Nn));
+	CCG_CHECK(hipStreamSynchronize(ctx->stream));
+	return CCG_OK;
 }
-#undef SNP_TRY
 
 // One matrix: the LT rows [rb, re) (world == 0) or one rank's rows of the band
 // layout (world > 0; rb = 0, re = n).  CCG_DIST_MFMA picks the kernels: 2 (the
@@ -2031,67 +2014,35 @@ int ccg_snp_shard_dev_impl(ccg_ctx *ctx, const ccg_snp_args *a, int rank, int wo
 }
 
 // the bit planes of every taxon.  host_in: a->seqs / a->incs are host memory,
-// streamed through a bounded staging buffer, so HBM holds the planes and the
-// LT only (configs[4]: 25 GB of planes beside a 250 GB shard, where a device
-// copy of the packed MSA would add another 25 GB).  *mask = the device copy of
-// the non-pair include mask (k_popsum reads it), or NULL.
-static int snp_planes(ccg_ctx *ctx, const ccg_snp_args *a, int W32, int Wp, void *planes, bool host_in,
-                      uint32_t **mask, const int *widx) {
-	*mask = NULL;
-	if(!host_in) {
-		const long long total = (long long) a->n * Wp, pg = cdivll(total, 256);
-		k_planes<<<(unsigned) (pg < 262144 ? pg : 262144), 256, 0, ctx->stream>>>(
-		    a->seqs, a->incs, a->n, a->stride, W32, Wp, a->pair, (uint2 *) planes, (uint4 *) planes, widx);
-		CCG_CHECK(hipGetLastError());
-		return CCG_OK;
-	}
-	const size_t row_b = (size_t) a->stride * 8 + (a->pair ? (size_t) a->stride * 4 : 0);
-	long long R = (long long) (((size_t) 256 << 20) / row_b);
-	if(R < 1) R = 1;
-	if(R > a->n) R = a->n;
-	void *stage = NULL;
-	CCG_CHECK(hipMalloc(&stage, (size_t) R * row_b));
-	if(!a->pair) {
-		if(hipMalloc((void **) mask, (size_t) a->stride * 4) != hipSuccess) {
-			hipFree(stage);
-			*mask = NULL;
-			return CCG_ENOMEM;
-		}
-		if(hipMemcpyAsync(*mask, a->incs, (size_t) a->stride * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-			hipFree(stage);
-			hipFree(*mask);
-			*mask = NULL;
-			return CCG_EHIP;
-		}
-	}
-	uint64_t *sseq = (uint64_t *) stage;
-	uint32_t *sinc = (uint32_t *) ((char *) stage + (size_t) R * a->stride * 8);
-	int rc = CCG_OK;
-	for(long long t0 = 0; t0 < a->n && rc == CCG_OK; t0 += R) {
-		const long long rows = a->n - t0 < R ? a->n - t0 : R;
-		// stream-ordered: the copy into the stage waits for the previous chunk's k_planes
-		if(hipMemcpyAsync(sseq, a->seqs + (size_t) t0 * a->stride, (size_t) rows * a->stride * 8,
-		                  hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-		   (a->pair && hipMemcpyAsync(sinc, a->incs + (size_t) t0 * a->stride, (size_t) rows * a->stride * 4,
-		                              hipMemcpyHostToDevice, ctx->stream) != hipSuccess)) {
-			rc = CCG_EHIP;
-			break;
-		}
+// streamed through a bounded staging buffer (ccg_stage_rows), so HBM holds the
+// planes and the LT only (configs[4]: 25 GB of planes beside a 250 GB shard,
+// where a device copy of the packed MSA would add another 25 GB).  mask: the
+// device copy of the non-pair include mask (k_popsum reads it), allocated here.
+static int snp_planes(ccg_ctx *ctx, const ccg_snp_args *a, int W32, int Wp, void *planes, bool host_in, DevMem &mask,
+                      const int *widx) {
+	const auto launch = [&](const uint64_t *seqs, const uint32_t *incs, long long t0, long long rows) {
 		const long long pg = cdivll(rows * Wp, 256);
 		k_planes<<<(unsigned) (pg < 262144 ? pg : 262144), 256, 0, ctx->stream>>>(
-		    sseq, a->pair ? sinc : *mask, (int) rows, a->stride, W32, Wp, a->pair, (uint2 *) planes + t0 * Wp,
-		    (uint4 *) planes + t0 * Wp, widx);
-		if(hipGetLastError() != hipSuccess) rc = CCG_EHIP;
+		    seqs, incs, (int) rows, a->stride, W32, Wp, a->pair, (uint2 *) planes + t0 * Wp, (uint4 *) planes + t0 * Wp,
+		    widx);
+		CCG_CHECK(hipGetLastError());
+		return CCG_OK;
+	};
+	if(!host_in) return launch(a->seqs, a->incs, 0, a->n);
+	if(!a->pair) {
+		CCG_TRY(mask.alloc((size_t) a->stride * 4));
+		CCG_CHECK(hipMemcpyAsync(mask.p, a->incs, (size_t) a->stride * 4, hipMemcpyHostToDevice, ctx->stream));
 	}
-	hipStreamSynchronize(ctx->stream);
-	hipFree(stage);
-	return rc;
+	return ccg_stage_rows(ctx->stream, a->seqs, a->incs, a->n, a->stride, a->pair != 0,
+	                      [&](const uint64_t *sseq, const uint32_t *sinc, long long t0, long long rows) {
+		                      return launch(sseq, a->pair ? sinc : mask.as<uint32_t>(), t0, rows);
+	                      });
 }
 
 static int snp_run(ccg_ctx *ctx, const ccg_snp_args *a, void *D, void *N, int *inc_out, int rank, int world,
                    bool host_in) {
 	if(!a || a->n < 0 || a->len <= 0 || a->stride < (a->len + 31) / 32) return CCG_EINVAL;
-	if(a->etype != 8 && a->etype != 4 && a->etype != 2 && a->etype != 1) return CCG_EINVAL;
+	if(!ccg_etype_ok(a->etype)) return CCG_EINVAL;
 	ctx->dist_slices = ctx->dist_slice_words = 0;   // until a launcher plans (n < 2 and -P's k_snp_pair_proxi: none)
 	if(a->n < 2) {
 		if(inc_out && !a->pair && host_in) {
@@ -2099,12 +2050,12 @@ static int snp_run(ccg_ctx *ctx, const ccg_snp_args *a, void *D, void *N, int *i
 			for(int w = 0; w < (a->len + 31) / 32; ++w) s += __builtin_popcount(a->incs[w]);
 			*inc_out = s;
 		} else if(inc_out && !a->pair) {
-			int *d_inc;
-			CCG_CHECK(hipMalloc(&d_inc, sizeof(int)));
-			k_popsum<<<1, 256, 0, ctx->stream>>>(a->incs, (a->len + 31) / 32, d_inc);
-			CCG_CHECK(hipMemcpyAsync(inc_out, d_inc, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+			DevMem d_inc;
+			CCG_TRY(d_inc.alloc(sizeof(int)));
+			StreamSync idle(ctx->stream);
+			k_popsum<<<1, 256, 0, ctx->stream>>>(a->incs, (a->len + 31) / 32, d_inc.as<int>());
+			CCG_CHECK(hipMemcpyAsync(inc_out, d_inc.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 			CCG_CHECK(hipStreamSynchronize(ctx->stream));
-			CCG_CHECK(hipFree(d_inc));
 		}
 		return CCG_OK;
 	}
@@ -2136,63 +2087,42 @@ static int snp_run(ccg_ctx *ctx, const ccg_snp_args *a, void *D, void *N, int *i
 	const int Wp = (int) (cdivll(Wc, kc) * kc);
 	const long long npad = cdivll(a->n, TILE2) * TILE2;   // whole panels of either tile size
 	const size_t esz = a->pair ? sizeof(uint4) : sizeof(uint2);
-	void *planes = NULL;
-	int *d_inc = NULL, *d_widx = NULL;
-	// a CCG_CTX_NOSYNC context (a pipeline's dist) keeps its planes in the
-	// workspace cache: no hipMalloc / hipFree per matrix (hipFree waits for
-	// every stream of the device, the other context's too)
-	// (with the small buffers behind them: the count and the word list)
-	const bool cached = (ctx->flags & CCG_CTX_NOSYNC) != 0;
 	const size_t planes_b = ((size_t) npad * Wp * esz + 255) & ~(size_t) 255;
-	auto free_bufs = [&]() {
-		if(cached) return;
-		hipFree(planes);
-		hipFree(d_inc);
-		hipFree(d_widx);
-	};
-	if(cached) {
-		const int wrc = ccg_ctx_workspace(ctx, 2, planes_b + 256 + keep.size() * sizeof(int), &planes);
-		if(wrc != CCG_OK) return wrc;
-		d_inc = (int *) ((char *) planes + planes_b);
-		if(!keep.empty()) d_widx = (int *) ((char *) planes + planes_b + 256);
+	// The planes, the included count, the compacted word list and (host_in) the
+	// non-pair mask.  A CCG_CTX_NOSYNC context (a pipeline's dist) borrows the
+	// first three from its workspace slot, the small ones behind the planes:
+	// no hipMalloc / hipFree per matrix (hipFree waits for every stream of the
+	// device, the other context's too).  Any other context owns them.
+	DevMem planes, d_inc, d_widx, mask;
+	if(ctx->flags & CCG_CTX_NOSYNC) {
+		void *ws = NULL;
+		CCG_TRY(ccg_ctx_workspace(ctx, CCG_WS_DIST, planes_b + 256 + keep.size() * sizeof(int), &ws));
+		planes.borrow(ws);
+		d_inc.borrow((char *) ws + planes_b);
+		if(!keep.empty()) d_widx.borrow((char *) ws + planes_b + 256);
 	} else {
-		CCG_CHECK(hipMalloc(&planes, planes_b));
-		if(hipMalloc(&d_inc, sizeof(int)) != hipSuccess ||
-		   (!keep.empty() && hipMalloc(&d_widx, keep.size() * sizeof(int)) != hipSuccess)) {
-			hipFree(planes);
-			hipFree(d_inc);
-			return CCG_ENOMEM;
-		}
+		CCG_TRY(planes.alloc(planes_b));
+		CCG_TRY(d_inc.alloc(sizeof(int)));
+		if(!keep.empty()) CCG_TRY(d_widx.alloc(keep.size() * sizeof(int)));
 	}
-	uint32_t *mask = NULL;
-	int prc = CCG_OK;
+	StreamSync idle(ctx->stream);   // (after the holders: no launch still reads them when they free)
 	// k_planes writes every word of rows < n: only the padding rows need zeros
-	if(hipMemsetAsync((char *) planes + (size_t) a->n * Wp * esz, 0, (size_t) (npad - a->n) * Wp * esz,
-	                  ctx->stream) != hipSuccess ||
-	   (d_widx && hipMemcpyAsync(d_widx, keep.data(), keep.size() * sizeof(int), hipMemcpyHostToDevice,
-	                             ctx->stream) != hipSuccess))
-		prc = CCG_EHIP;
-	if(!prc) {
-		// the compacted word list, or every word (a mask with no included word: one zero word)
-		const int *widx = d_widx;
-		const int Wsrc = d_widx ? Wc : (a->pair || Wc == W32 ? W32 : 0);
-		prc = snp_planes(ctx, a, Wsrc, Wp, planes, host_in, &mask, widx);
-	}
-	if(prc) {
-		hipStreamSynchronize(ctx->stream);
-		free_bufs();
-		hipFree(mask);
-		return prc;
-	}
+	CCG_CHECK(hipMemsetAsync(planes.p + (size_t) a->n * Wp * esz, 0, (size_t) (npad - a->n) * Wp * esz, ctx->stream));
+	if(d_widx.p)
+		CCG_CHECK(hipMemcpyAsync(d_widx.p, keep.data(), keep.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+	// the compacted word list, or every word (a mask with no included word: one zero word)
+	const int Wsrc = d_widx.p ? Wc : (a->pair || Wc == W32 ? W32 : 0);
+	CCG_TRY(snp_planes(ctx, a, Wsrc, Wp, planes.p, host_in, mask, d_widx.as<int>()));
 	int inc = 0;
 	if(!a->pair) {
-		k_popsum<<<1, 1024, 0, ctx->stream>>>(mask ? mask : a->incs, W32, d_inc);
-		CCG_CHECK(hipMemcpyAsync(&inc, d_inc, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+		k_popsum<<<1, 1024, 0, ctx->stream>>>(mask.p ? mask.as<uint32_t>() : a->incs, W32, d_inc.as<int>());
+		CCG_CHECK(hipMemcpyAsync(&inc, d_inc.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 		CCG_CHECK(hipStreamSynchronize(ctx->stream));
 	}
-	if(mask) CCG_CHECK(hipFree(mask));
-	if(d_widx && !cached) CCG_CHECK(hipFree(d_widx));
-	d_widx = NULL;
+	// the stream is idle in non-pair mode (the read-back above); in pair mode
+	// neither exists
+	mask.release();
+	d_widx.release();
 	double nFactor = 1.0;
 	if(!a->pair && a->norm) {
 		nFactor = a->norm;
@@ -2200,28 +2130,18 @@ static int snp_run(ccg_ctx *ctx, const ccg_snp_args *a, void *D, void *N, int *i
 	}
 	long long rb = a->row_begin, re = a->row_end;
 	if(rb == 0 && re == 0) re = a->n;
-	if(rb < 0 || re > a->n || rb > re) {
-		free_bufs();
-		return CCG_EINVAL;
-	}
+	if(rb < 0 || re > a->n || rb > re) return CCG_EINVAL;
 	int rc = CCG_OK;
 	ctx->dist_ms = 0;
 	CCG_CHECK(hipEventRecord(ctx->ev0, ctx->stream));
 	if(re > rb) {   // a shard takes every row: rb = 0, re = n
-		switch(a->etype) {
-			case 8: rc = snp_launch<8>(ctx, a, planes, Wp, nFactor, D, N, rb, re, rank, world); break;
-			case 4: rc = snp_launch<4>(ctx, a, planes, Wp, nFactor, D, N, rb, re, rank, world); break;
-			case 2: rc = snp_launch<2>(ctx, a, planes, Wp, nFactor, D, N, rb, re, rank, world); break;
-			default: rc = snp_launch<1>(ctx, a, planes, Wp, nFactor, D, N, rb, re, rank, world); break;
-		}
+		rc = with_etype(a->etype, [&](auto et) {
+			return snp_launch<decltype(et)::value>(ctx, a, planes.p, Wp, nFactor, D, N, rb, re, rank, world);
+		});
 	}
 	CCG_CHECK(hipEventRecord(ctx->ev1, ctx->stream));
 	CCG_CHECK(hipStreamSynchronize(ctx->stream));
 	if(rc == CCG_OK) CCG_CHECK(hipEventElapsedTime(&ctx->dist_ms, ctx->ev0, ctx->ev1));
-	if(!cached) {
-		CCG_CHECK(hipFree(planes));
-		CCG_CHECK(hipFree(d_inc));
-	}
 	if(inc_out) *inc_out = inc;
 	return rc;
 }
@@ -2288,8 +2208,10 @@ extern "C" int ccg_round_decimal_dev(ccg_ctx *ctx, void *D, int64_t elems, int e
 	if(!elems) return CCG_OK;
 	double P = 1.0;
 	for(int k = 0; k < precision; ++k) P *= 10.0;   // exact up to 10^22
-	int *d_bad = NULL, bad = 0;
-	CCG_CHECK(hipMalloc(&d_bad, sizeof(int)));
+	DevMem flag;
+	CCG_TRY(flag.alloc(sizeof(int)));
+	StreamSync idle(ctx->stream);
+	int *d_bad = flag.as<int>(), bad = 0;
 	CCG_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), ctx->stream));
 	const long long g = cdivll(elems, 256);
 	const unsigned grid = (unsigned) (g < 65536 ? g : 65536);
@@ -2298,7 +2220,6 @@ extern "C" int ccg_round_decimal_dev(ccg_ctx *ctx, void *D, int64_t elems, int e
 	CCG_CHECK(hipGetLastError());
 	CCG_CHECK(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 	CCG_CHECK(hipStreamSynchronize(ctx->stream));
-	CCG_CHECK(hipFree(d_bad));
 	if(bad) {
 		ccg_set_last_msg("ccg_round_decimal_dev: a cell needs more than 15 significant digits at this precision");
 		return CCG_EUNSUP;

@@ -1763,21 +1763,20 @@ static size_t tree_layout(TreeBufs *bp, int n, char *m) {
 
 size_t ccg_tree_bytes(int n) { return tree_layout(NULL, n, NULL); }
 
-int ccg_tree_alloc(TreeWork *w, int n, hipStream_t st) {
+int ccg_tree_alloc(DevMem &mem, TreeWork *w, int n, hipStream_t st) {
 	const size_t sz = tree_layout(NULL, n, NULL);
-	char *m;
-	CCG_CHECK(hipMalloc((void **) &m, sz));
-	CCG_CHECK(hipMemsetAsync(m, 0, sz, st));
-	w->mem = m;
-	tree_layout(&w->b, n, m);
+	CCG_TRY(mem.alloc(sz));
+	CCG_CHECK(hipMemsetAsync(mem.p, 0, sz, st));
+	w->mem = mem.p;
+	tree_layout(&w->b, n, mem.p);
 	return CCG_OK;
 }
 
-// the single engine's workspace: the context's cached slot 0 (no hipFree per run)
+// the single engine's workspace: the context's cached tree slot (no hipFree per run)
 static int tree_alloc_ctx(ccg_ctx *c, TreeWork *w, int n) {
 	const size_t sz = tree_layout(NULL, n, NULL);
 	void *m;
-	const int rc = ccg_ctx_workspace(c, 0, sz, &m);
+	const int rc = ccg_ctx_workspace(c, CCG_WS_TREE, sz, &m);
 	if(rc) return rc;
 	CCG_CHECK(hipMemsetAsync(m, 0, sz, c->stream));
 	w->mem = m;
@@ -2083,7 +2082,7 @@ static int tree_run_t(ccg_ctx *ctx, const ccg_tree_args *a, void *Dd, ccg_join *
 	if(a->method == CCG_TREE_DNJ && !general && g_grid.lb && n0 > g_grid.lb_min_n) {
 		const LbLayout lb = lb_layout(n0, n0);
 		void *lbmem = NULL;
-		if(ccg_ctx_workspace(ctx, 1, lb.bytes(), &lbmem) == CCG_OK) {
+		if(ccg_ctx_workspace(ctx, CCG_WS_TREE_LB, lb.bytes(), &lbmem) == CCG_OK) {
 			CCG_TRY(lb_bind(b, lbmem, lb, 0, st));
 			k_lb_init<ET><<<cdiv(n0, TB / 64), TB, 0, st>>>(D, n0, bs, b);
 			launches += 1;
@@ -2192,8 +2191,10 @@ __global__ __launch_bounds__(NT) void k_selftest_row_sum(TreeBufs b, int n, doub
 
 int ccg_selftest_row_sum_impl(ccg_ctx *ctx, const double *c, int n, double *out, int *parallel) {
 	hipStream_t st = ctx->stream;
-	char *m;
-	CCG_CHECK(hipMalloc((void **) &m, (size_t) (n + 1) * 8 + 64 + 64 * 8));
+	DevMem mem;
+	CCG_TRY(mem.alloc((size_t) (n + 1) * 8 + 64 + 64 * 8));
+	StreamSync idle(st);
+	char *m = mem.p;
 	TreeBufs b;
 	memset(&b, 0, sizeof(b));
 	b.contrib = (double *) m;
@@ -2232,7 +2233,6 @@ int ccg_selftest_row_sum_impl(ccg_ctx *ctx, const double *c, int n, double *out,
 	CCG_CHECK(hipMemcpyAsync(out, dout, 8, hipMemcpyDeviceToHost, st));
 	CCG_CHECK(hipMemcpyAsync(parallel, dpar, 4, hipMemcpyDeviceToHost, st));
 	CCG_CHECK(hipStreamSynchronize(st));
-	CCG_CHECK(hipFree(m));
 	return CCG_OK;
 }
 
@@ -2245,11 +2245,8 @@ int ccg_tree_impl(ccg_ctx *ctx, const ccg_tree_args *a, void *Dd, ccg_join *join
 	// NJ (and MN, its argmax form), DNJ and HNJ are the loops below; any other id must not fall through to NJ
 	if(a->method != CCG_TREE_NJ && a->method != CCG_TREE_DNJ && a->method != CCG_TREE_HNJ && a->method != CCG_TREE_MN)
 		return CCG_EINVAL;
-	switch(a->etype) {
-		case 8: return tree_run_t<8>(ctx, a, Dd, joins, njoins, final_n, final_d, stats, sin, sout);
-		case 4: return tree_run_t<4>(ctx, a, Dd, joins, njoins, final_n, final_d, stats, sin, sout);
-		case 2: return tree_run_t<2>(ctx, a, Dd, joins, njoins, final_n, final_d, stats, sin, sout);
-		case 1: return tree_run_t<1>(ctx, a, Dd, joins, njoins, final_n, final_d, stats, sin, sout);
-		default: return CCG_EINVAL;
-	}
+	if(!ccg_etype_ok(a->etype)) return CCG_EINVAL;
+	return with_etype(a->etype, [&](auto et) {
+		return tree_run_t<decltype(et)::value>(ctx, a, Dd, joins, njoins, final_n, final_d, stats, sin, sout);
+	});
 }

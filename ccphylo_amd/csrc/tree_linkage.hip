@@ -675,7 +675,7 @@ static int lk_run_t(ccg_ctx *ctx, const ccg_tree_args *a, void *Dd, ccg_join *jo
 	hipStream_t st = ctx->stream;
 	void *mem;
 	const size_t sz = lk_layout(NULL, n0, NULL);
-	int rc = ccg_ctx_workspace(ctx, 0, sz, &mem);
+	int rc = ccg_ctx_workspace(ctx, CCG_WS_TREE, sz, &mem);
 	if(rc) return rc;
 	CCG_CHECK(hipMemsetAsync(mem, 0, sz, st));
 	LkBufs b;
@@ -730,11 +730,8 @@ static int lk_run_t(ccg_ctx *ctx, const ccg_tree_args *a, void *Dd, ccg_join *jo
 // CCG_TREE_UPGMA / CCG_TREE_CF / CCG_TREE_FF on a device LT (consumed)
 int ccg_tree_linkage_impl(ccg_ctx *ctx, const ccg_tree_args *a, void *Dd, ccg_join *joins, int *njoins, int *final_n,
                           double *final_d, int64_t *stats) {
-	switch(a->etype) {
-		case 8: return lk_run_t<8>(ctx, a, Dd, joins, njoins, final_n, final_d, stats);
-		case 4: return lk_run_t<4>(ctx, a, Dd, joins, njoins, final_n, final_d, stats);
-		case 2: return lk_run_t<2>(ctx, a, Dd, joins, njoins, final_n, final_d, stats);
-		case 1: return lk_run_t<1>(ctx, a, Dd, joins, njoins, final_n, final_d, stats);
-		default: return CCG_EINVAL;
-	}
+	if(!ccg_etype_ok(a->etype)) return CCG_EINVAL;
+	return with_etype(a->etype, [&](auto et) {
+		return lk_run_t<decltype(et)::value>(ctx, a, Dd, joins, njoins, final_n, final_d, stats);
+	});
 }

@@ -25,6 +25,7 @@
 #include <pthread.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <memory>
 #include <rccl/rccl.h>
 #define CCG_DNJ_NO_TRACE
 #include "ccg_tree_run.h"
@@ -778,7 +779,7 @@ static int tree_shard_run_t(ccg_ctx *ctx, const ccg_tree_args *a, const ccg_coll
 	if(hnj && cdiv(n0, TB) > SH_GRID) return CCG_EINVAL;   // the minQ partials (one per 256 rows)
 	const ShnLayout L(n0, coll_in->world, ET, hnj);
 	DevMem mem;
-	if(!mem.alloc(L.sz)) return CCG_ENOMEM;
+	CCG_TRY(mem.alloc(L.sz));
 	char *m = mem.p;
 	size_t hcap = sh_init_host_bytes(n0, coll_in->world);
 	if((size_t) 2 * n0 * ET > hcap) hcap = (size_t) 2 * n0 * ET;
@@ -973,7 +974,7 @@ static int shard_linkage_unsup(int method) {
 
 int ccg_tree_shard_bytes(int64_t n, int etype, int method, int world, int64_t *device_bytes, int64_t *gather_bytes) {
 	if(!device_bytes || n < 3 || n > INT32_MAX - 512 || world < 1) return CCG_EINVAL;
-	if(etype != 8 && etype != 4 && etype != 2 && etype != 1) return CCG_EINVAL;
+	if(!ccg_etype_ok(etype)) return CCG_EINVAL;
 	if(shard_linkage_unsup(method)) return CCG_EUNSUP;
 	if(method != CCG_TREE_NJ && method != CCG_TREE_DNJ && method != CCG_TREE_HNJ) return CCG_EINVAL;
 	const int n0 = (int) n;
@@ -1020,8 +1021,7 @@ static int shard_check(ccg_ctx *c, const ccg_tree_args *a, const ccg_coll *coll)
 	if(!c || !a) return CCG_EINVAL;
 	if(a->n < 3 || (a->method != CCG_TREE_NJ && a->method != CCG_TREE_DNJ && a->method != CCG_TREE_HNJ))
 		return CCG_EINVAL;
-	if(a->etype != 8 && a->etype != 4 && a->etype != 2 && a->etype != 1) return CCG_EINVAL;
-	if((a->etype == 2 || a->etype == 1) && !(a->byteScale != 0)) return CCG_EINVAL;
+	if(!ccg_etype_ok(a->etype) || !ccg_etype_scale_ok(a->etype, a->byteScale)) return CCG_EINVAL;
 	if(coll && (coll->world < 1 || coll->rank < 0 || coll->rank >= coll->world || !coll->allreduce_sum_u8 ||
 	            !coll->broadcast))
 		return CCG_EINVAL;
@@ -1035,8 +1035,7 @@ int ccg_tree_shard_dev(ccg_ctx *c, const ccg_tree_args *a, const ccg_coll *coll,
 		if(!Dloc || !joins || !njoins || !final_n || !final_d) return CCG_EINVAL;
 		if(a->n < 3 || (a->method != CCG_TREE_NJ && a->method != CCG_TREE_DNJ && a->method != CCG_TREE_HNJ))
 			return CCG_EINVAL;
-		if(a->etype != 8 && a->etype != 4 && a->etype != 2 && a->etype != 1) return CCG_EINVAL;
-		if((a->etype == 2 || a->etype == 1) && !(a->byteScale != 0)) return CCG_EINVAL;
+		if(!ccg_etype_ok(a->etype) || !ccg_etype_scale_ok(a->etype, a->byteScale)) return CCG_EINVAL;
 		CCG_CHECK(hipSetDevice(c->device));
 		CCG_DEVICE_SYNC(c);
 		return ccg_tree_impl(c, a, Dloc, joins, njoins, final_n, final_d, stats, NULL, NULL);
@@ -1054,12 +1053,9 @@ int ccg_tree_shard_dev(ccg_ctx *c, const ccg_tree_args *a, const ccg_coll *coll,
 		}
 		return ccg_tree_shard_dnj_impl(c, a, coll, Dloc, joins, njoins, final_n, final_d, stats);
 	}
-	switch(a->etype) {
-		case 8: return tree_shard_run_t<8>(c, a, coll, Dloc, joins, njoins, final_n, final_d, stats);
-		case 4: return tree_shard_run_t<4>(c, a, coll, Dloc, joins, njoins, final_n, final_d, stats);
-		case 2: return tree_shard_run_t<2>(c, a, coll, Dloc, joins, njoins, final_n, final_d, stats);
-		default: return tree_shard_run_t<1>(c, a, coll, Dloc, joins, njoins, final_n, final_d, stats);
-	}
+	return with_etype(a->etype, [&](auto et) {
+		return tree_shard_run_t<decltype(et)::value>(c, a, coll, Dloc, joins, njoins, final_n, final_d, stats);
+	});
 }
 
 int ccg_tree_shard(ccg_ctx *c, const ccg_tree_args *a, const ccg_coll *coll, const void *D, ccg_join *joins,
@@ -1072,28 +1068,20 @@ int ccg_tree_shard(ccg_ctx *c, const ccg_tree_args *a, const ccg_coll *coll, con
 	const int64_t n = a->n, es = a->etype;
 	const int64_t elems = ccg_shard_elems(n, rank, world);
 	// the rank's bands are contiguous row runs of the full LT: copy band by band
-	char *hbuf = (char *) malloc((size_t) (elems ? elems : 1) * es);
+	const std::unique_ptr<char, void (*)(void *)> hbuf((char *) malloc((size_t) (elems ? elems : 1) * es), free);
 	if(!hbuf) return CCG_ENOMEM;
 	const char *src = (const char *) D;
 	for(int64_t g = rank; g * SB < n; g += world) {
 		const int64_t r0 = g * SB, r1 = r0 + SB < n ? r0 + SB : n;
-		memcpy(hbuf + ccg_shard_row_offset(r0, rank, world) * es, src + tri(r0) * es, (size_t) (tri(r1) - tri(r0)) * es);
+		memcpy(hbuf.get() + ccg_shard_row_offset(r0, rank, world) * es, src + tri(r0) * es,
+		       (size_t) (tri(r1) - tri(r0)) * es);
 	}
 	CCG_CHECK(hipSetDevice(c->device));
-	void *d = NULL;
-	if(hipMalloc(&d, (size_t) (elems ? elems : 1) * es) != hipSuccess) {
-		free(hbuf);
-		return CCG_ENOMEM;
-	}
-	if(hipMemcpy(d, hbuf, (size_t) elems * es, hipMemcpyHostToDevice) != hipSuccess) {
-		rc = CCG_EHIP;
-	} else {
-		rc = ccg_tree_shard_dev(c, a, coll, d, joins, njoins, final_n, final_d, stats);
-	}
-	free(hbuf);
-	hipStreamSynchronize(c->stream);
-	hipFree(d);
-	return rc;
+	DevMem d;
+	CCG_TRY(d.alloc((size_t) elems * es));
+	StreamSync idle(c->stream);
+	CCG_CHECK(hipMemcpy(d.p, hbuf.get(), (size_t) elems * es, hipMemcpyHostToDevice));
+	return ccg_tree_shard_dev(c, a, coll, d.p, joins, njoins, final_n, final_d, stats);
 }
 
 }   // extern "C"

@@ -816,12 +816,12 @@ static int tree_shard_dnj_run_t(ccg_ctx *ctx, const ccg_tree_args *a, const ccg_
 	hipStream_t st = ctx->stream;
 	const Shard sh = {coll->rank, coll->world};
 	TreeWork w;
-	CCG_TRY(ccg_tree_alloc(&w, n0, st));
-	DevMem wmem(w.mem), mem, lbmem, dbgmem;
+	DevMem wmem, mem, lbmem, dbgmem;
+	CCG_TRY(ccg_tree_alloc(wmem, &w, n0, st));
 	TreeBufs b = w.b;
 	const ShdLayout L(n0, coll->world, ET);
 	const RecSlot rs0 = rec_slot(n0, coll->world);
-	if(!mem.alloc(L.sz)) return CCG_ENOMEM;
+	CCG_TRY(mem.alloc(L.sz));
 	char *m = mem.p;
 	size_t hcap = sh_init_host_bytes(n0, coll->world);
 	if((size_t) 3 * n0 * ET > hcap) hcap = (size_t) 3 * n0 * ET;
@@ -837,7 +837,7 @@ static int tree_shard_dnj_run_t(ccg_ctx *ctx, const ccg_tree_args *a, const ccg_
 	unsigned char *pflag = (unsigned char *) (m + L.o_pf), *pacc = (unsigned char *) (m + L.o_pa);
 	unsigned *pcnt = (unsigned *) (m + L.o_pc);
 	unsigned long long *dbg = NULL;
-	if(getenv("CCG_PICK_TS") && dbgmem.alloc(1024 * 8 * 8) && hipMemsetAsync(dbgmem.p, 0, 1024 * 8 * 8, st) == hipSuccess)
+	if(getenv("CCG_PICK_TS") && dbgmem.alloc(1024 * 8 * 8) == CCG_OK && hipMemsetAsync(dbgmem.p, 0, 1024 * 8 * 8, st) == hipSuccess)
 		dbg = (unsigned long long *) dbgmem.p;
 	const TreeCtl init = tree_ctl_seed(a);
 	TreeRun<TreeCtl> run(ctx, b.ctl);   // (after the memory: it waits for the stream before that is freed)
@@ -854,7 +854,7 @@ static int tree_shard_dnj_run_t(ccg_ctx *ctx, const ccg_tree_args *a, const ccg_
 	// owned row, the sD maxima and the thresholds replicated
 	if(grid.lb && n0 > grid.lb_min_n) {
 		const LbLayout lb = lb_layout(n0, (long long) cdiv(cdiv(n0, 8), sh.world) * 8);
-		if(lbmem.alloc(lb.bytes())) {   // (no room: the run goes without, the same joins)
+		if(lbmem.alloc(lb.bytes()) == CCG_OK) {   // (no room: the run goes without, the same joins)
 			CCG_TRY(lb_bind(b, lbmem.p, lb, sh.world, st));
 			k_shd_lb_init<ET><<<cdiv(n0, TB / 64), TB, 0, st>>>(D, n0, bs, b, sh);
 			CCG_CHECK(hipGetLastError());
@@ -937,10 +937,7 @@ static int tree_shard_dnj_run_t(ccg_ctx *ctx, const ccg_tree_args *a, const ccg_
 // arguments already checked there, coll non-null
 int ccg_tree_shard_dnj_impl(ccg_ctx *c, const ccg_tree_args *a, const ccg_coll *coll, void *Dloc, ccg_join *joins,
                             int *njoins, int *final_n, double *final_d, int64_t *stats) {
-	switch(a->etype) {
-		case 8: return tree_shard_dnj_run_t<8>(c, a, coll, Dloc, joins, njoins, final_n, final_d, stats);
-		case 4: return tree_shard_dnj_run_t<4>(c, a, coll, Dloc, joins, njoins, final_n, final_d, stats);
-		case 2: return tree_shard_dnj_run_t<2>(c, a, coll, Dloc, joins, njoins, final_n, final_d, stats);
-		default: return tree_shard_dnj_run_t<1>(c, a, coll, Dloc, joins, njoins, final_n, final_d, stats);
-	}
+	return with_etype(a->etype, [&](auto et) {
+		return tree_shard_dnj_run_t<decltype(et)::value>(c, a, coll, Dloc, joins, njoins, final_n, final_d, stats);
+	});
 }

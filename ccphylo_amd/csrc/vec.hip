@@ -293,7 +293,7 @@ static int vec_run(ccg_ctx *c, const ccg_vec_args *a, void *D) {
 	c->vec_tile = 0;
 	if(a->m < 2) return CCG_OK;
 	void *ws = NULL;
-	int rc = ccg_ctx_workspace(c, 4, 2 * (size_t) a->m * sizeof(double), &ws);
+	int rc = ccg_ctx_workspace(c, CCG_WS_VEC, 2 * (size_t) a->m * sizeof(double), &ws);
 	if(rc) return rc;
 	const double *r0 = (const double *) ws, *r1 = r0 + a->m;
 	const int tile = vec_tile(a->m);
@@ -331,28 +331,18 @@ int ccg_vec_ltd(ccg_ctx *c, const ccg_vec_args *a, void *D) {
 	CCG_CHECK(hipSetDevice(c->device));
 	const size_t m = (size_t) a->m, rowb = (size_t) a->n * (size_t) a->vtype;
 	const size_t xb = (m * rowb + 255) & ~(size_t) 255, lt = m * (m - 1) / 2 * (size_t) a->etype;
-	char *mem = NULL;
-	if(hipMalloc((void **) &mem, xb + lt) != hipSuccess) {
-		(void) hipGetLastError();
-		return CCG_ENOMEM;
-	}
-	ccg_vec_args d = *a;
-	d.X = mem;
-	d.stride = a->n;   // packed on the way up
+	DevMem mem;
+	CCG_TRY(mem.alloc(xb + lt));
 	hipStream_t st = c->stream;
-	if(hipMemcpy2DAsync(mem, rowb, a->X, (size_t) a->stride * (size_t) a->vtype, rowb, m, hipMemcpyHostToDevice, st) !=
-	   hipSuccess) {
-		rc = CCG_EHIP;
-	} else {
-		rc = vec_run(c, &d, mem + xb);
-	}
-	if(!rc && (hipMemcpyAsync(D, mem + xb, lt, hipMemcpyDeviceToHost, st) != hipSuccess ||
-	           hipStreamSynchronize(st) != hipSuccess)) {
-		rc = CCG_EHIP;
-	}
-	hipStreamSynchronize(st);
-	hipFree(mem);
-	return rc;
+	StreamSync idle(st);
+	ccg_vec_args d = *a;
+	d.X = mem.p;
+	d.stride = a->n;   // packed on the way up
+	CCG_CHECK(hipMemcpy2DAsync(mem.p, rowb, a->X, (size_t) a->stride * (size_t) a->vtype, rowb, m, hipMemcpyHostToDevice, st));
+	CCG_TRY(vec_run(c, &d, mem.p + xb));
+	CCG_CHECK(hipMemcpyAsync(D, mem.p + xb, lt, hipMemcpyDeviceToHost, st));
+	CCG_CHECK(hipStreamSynchronize(st));
+	return CCG_OK;
 }
 
 int ccg_last_vec_ms(ccg_ctx *c, double *ms) {

@@ -72,10 +72,14 @@ int ccg_init(int device, ccg_ctx **ctx);
  * each masked configuration keeps one HIP stream until the process exits.
  * flags CCG_CTX_NOSYNC: the device-pointer entry points do not wait for the
  * whole device first (the caller orders its inputs; a device-wide wait would
- * wait for the other context's work), and the context keeps its workspaces
- * -- the tree's, and the dist's bit planes (about n x L / 4 bytes) -- until
- * ccg_destroy, so that no call frees device memory (hipFree waits for every
- * stream of the device). */
+ * wait for the other context's work), and the context also keeps the dist's
+ * bit planes (about n x L / 4 bytes) until ccg_destroy, so that no dist call
+ * frees device memory (hipFree waits for every stream of the device).
+ * Every context, with or without the flag, keeps the workspaces of the tree
+ * (its run state and DNJ's block bounds), of dbscan, of the vec pre-pass and
+ * of the motif masking from their first use until ccg_destroy, each grown to
+ * the largest run so far; without the flag the dist allocates its planes per
+ * call and frees them with it. */
 #define CCG_CTX_NOSYNC 1
 int ccg_ctx_configure(ccg_ctx *ctx, const uint32_t *cu_mask, int mask_words, int flags);
 /* Process end, after the last HIP work of the process: destroys the CU-masked
