@@ -45,6 +45,7 @@ enum ccg_ws_slot {
 	CCG_WS_DBSCAN,    // dbscan's per-row vectors and counters
 	CCG_WS_VEC,       // the vec pre-pass's per-row values
 	CCG_WS_METH,      // the motif masking's counters
+	CCG_WS_FIT,       // the split prefix of the Newick replay; the LT comparison's perm, block partials and sums
 	CCG_WS_COUNT
 };
 
@@ -58,6 +59,9 @@ struct ccg_ctx {
 	float vec_ms;    // the last vec call's pre-pass and pair kernel (the same events)
 	int vec_pending; // ... still to be read from the events (a CCG_CTX_NOSYNC call)
 	int vec_tile;    // its tile edge (0: nothing launched)
+	float nwck_ms;   // the last Newick replay's kernels (the same events)
+	long long nwck_launches;   // ... and how many there were
+	float cmp_ms;    // the last LT comparison's two kernels
 	int flags;       // CCG_CTX_* (ccg_ctx_configure)
 	int masked;      // the stream was created with a CU mask (ccg_ctx_configure)
 	int ncu, cus;    // the device's CUs; the CUs the stream may use (0: all)

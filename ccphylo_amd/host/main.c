@@ -1,5 +1,5 @@
 /*
- * main.c -- `ccphylo dist`, `ccphylo tree`, `ccphylo dbscan` and `ccphylo tsv2phy`, the stable
+ * main.c -- `ccphylo dist`, `tree`, `dbscan`, `tsv2phy`, `nwck2phy` and `phycmp`, the stable
  * CLI surface, with the hot path on the GPU engine (include/ccphylo_amd.h).
  *
  * Mirrors ref main.c:99 (dispatch), dist.c:473 main_dist / :42 makeMatrix /
@@ -17,7 +17,10 @@
  * `--transport`, `--fast_sums` as for tree); `dist --dbscan FILE
  * [--max_distance E] [--min_neighbors N]` clusters that LT in HBM the same way
  * (alone, or before --tree); `tsv2phy --tree FILE [--tree_method M]` hands
- * the table's LT to the tree in HBM, and writes the Phylip text only with -o.
+ * the table's LT to the tree in HBM, and writes the Phylip text only with -o;
+ * `tree --phycmp FILE [--phycmp_flag F]` replays each tree's path lengths in
+ * HBM and writes the `phycmp` lines of matrix against tree to FILE;
+ * `phycmp --by_name` maps the second matrix's rows onto the first's by name.
  */
 #include <ctype.h>
 #include <errno.h>
@@ -108,6 +111,8 @@ static int tree_help(FILE *out) {
 	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "gpus", "Shard the matrix over G GPUs (nj, dnj)", "off");
 	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "transport", "rccl / host collectives for --gpus", "rccl");
 	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "fast_sums", "Parallel row sums (not the reference's)", "False");
+	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "phycmp", "Compare each tree's path lengths with its matrix", "off");
+	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "phycmp_flag", "phycmp -f flags for --phycmp", "1");
 	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "device", "First GPU", "0");
 	return out == stderr;
 }
@@ -120,8 +125,58 @@ static int transport_id(const char *v) {
 	return -1;
 }
 
+static int perm_by_name(char **names1, char **names2, int n, int32_t *perm, char *msg, size_t msglen);
+
+/* tree --phycmp: how well the tree just written represents its matrix.  The
+ * very string `nwck` is parsed as `nwck2phy` parses it, its splits are
+ * replayed into W_dev (n(n-1)/2 cells, free by now), the rows are mapped onto
+ * the matrix's by name, and A_dev -- the matrix as loaded -- is compared with
+ * it as `phycmp --by_name matrix tree-matrix` does.  0, or 1 with a message. */
+static int tree_phycmp(ccg_ctx *ctx, FILE *cmp, int cmpflag, const char *nwck, char **taxa, int n, int et,
+                       const void *A_dev, void *W_dev) {
+	char **leaves = NULL;
+	ccq_split *splits = NULL;
+	int nl = 0, rc;
+	if(n < 2) {
+		fprintf(stderr, "ccphylo_amd: tree --phycmp: a matrix of one entry has no distance to compare.\n");
+		return 1;
+	}
+	const size_t errlen = strlen(nwck) + 128;   /* a message quotes the node, which may be most of the string */
+	char *err = malloc(errlen);
+	if((rc = ccq_newick_splits(nwck, strlen(nwck), NULL, &leaves, &splits, &nl, err, errlen))) {
+		fprintf(stderr, rc > 0 ? "%s\n" : "ccphylo_amd: tree --phycmp: %s\n", err);
+		free(err);
+		return 1;
+	}
+	int32_t *perm = malloc((size_t) n * sizeof(int32_t));
+	int bad = 0;
+	if(nl != n) {
+		fprintf(stderr, "ccphylo_amd: tree --phycmp: the tree has %d leaves for %d entries of the matrix.\n", nl, n);
+		bad = 1;
+	} else if(perm_by_name(taxa, leaves, n, perm, err, errlen)) {
+		fprintf(stderr, "ccphylo_amd: tree --phycmp: the tree's leaves do not map one to one onto the matrix's entries: %s.\n", err);
+		bad = 1;
+	}
+	if(!bad) {
+		ccg_cmp_sums sums;
+		if((rc = ccg_nwck_ltd_dev(ctx, (const ccg_split *) splits, n - 1, et, W_dev)) ||
+		   (rc = ccg_ltd_cmp_dev(ctx, A_dev, W_dev, n, et, perm, &sums))) {
+			fprintf(stderr, "ccphylo_amd: tree --phycmp failed: %s\n", ccg_strerror(rc));
+			bad = 1;
+		} else {
+			ccq_print_phycmp(cmp, &sums, (int64_t) n * (n - 1) / 2, cmpflag);
+			fflush(cmp);
+		}
+	}
+	free(perm);
+	free(err);
+	ccq_newick_splits_free(leaves, splits, nl);
+	return bad;
+}
+
 static int main_tree(int argc, char **argv) {
-	const char *in = "-", *outname = "-", *method = "dnj";
+	const char *in = "-", *outname = "-", *method = "dnj", *cmpname = NULL;
+	int cmpflag = 1;
 	int flag = 0, precision = 9, et = 8, fast = 0, device = 0, stats = 0, gpus = 0, transport = CCQ_TRANSPORT_RCCL;
 	char sep = '\t', quotes = 0;
 	double bs = 1.0;
@@ -164,6 +219,8 @@ static int main_tree(int argc, char **argv) {
 			else if(!strcmp(name, "gpus")) gpus = (int) opt_num(&A, att, "gpus");
 			else if(!strcmp(name, "transport")) transport = transport_id(opt_value(&A, att, "transport"));
 			else if(!strcmp(name, "stats")) stats = 1;
+			else if(!strcmp(name, "phycmp")) cmpname = opt_value(&A, att, "phycmp");
+			else if(!strcmp(name, "phycmp_flag")) cmpflag = (int) opt_num(&A, att, "phycmp_flag");
 			else if(!strcmp(name, "help")) return tree_help(stdout);
 			else die_opt("Unknown", a);
 			continue;
@@ -241,6 +298,10 @@ static int main_tree(int argc, char **argv) {
 		fprintf(stderr, "ccphylo_amd: --gpus with tree method \"%s\" is not supported: the sharded engine runs nj, dnj and hnj.\n", method);
 		return 1;
 	}
+	if(cmpname && (gpus || et == 2 || et == 1)) {
+		fprintf(stderr, "ccphylo_amd: tree --phycmp with %s is not implemented.\n", gpus ? "--gpus" : "short / byte precision (-s / -b)");
+		return 1;
+	}
 
 	FILE *out = (outname[0] == '-' && outname[1] == 0) ? stdout : fopen(outname, "wb");
 	if(!out) {
@@ -252,10 +313,18 @@ static int main_tree(int argc, char **argv) {
 		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
 		return errno ? errno : 1;
 	}
+	FILE *cmp = NULL;
+	if(cmpname && !(cmp = fopen(cmpname, "wb"))) {
+		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
+		return errno ? errno : 1;
+	}
 	ccg_ctx *ctx = NULL;
 	ccq_ltd *D = ccq_ltd_new(32, et, bs);        /* tree.c:52 */
 	ccq_names *T = ccq_names_new(32, 4);         /* tree.c:61-66 */
 	int err = 0, n;
+	/* --phycmp: the entries' names and a device copy of the matrix, taken before the tree consumes either */
+	char **taxa = NULL;
+	void *A_dev = NULL, *W_dev = NULL;
 	ccg_join *joins = NULL;
 	size_t jcap = 0;
 	clock_t t0 = clock(), t1;
@@ -263,6 +332,20 @@ static int main_tree(int argc, char **argv) {
 		t1 = clock();
 		fprintf(stderr, "# Total time used loading matrix: %.2f s.\n", (double) (t1 - t0) / 1000000);
 		t0 = t1;
+		if(cmp) {
+			taxa = malloc((size_t) n * sizeof(char *));
+			for(int i = 0; i < n; ++i) taxa[i] = strdup((char *) T->names[i]->seq);
+			if(n >= 2) {
+				if(!ctx) ctx = open_gpu(device);
+				const size_t bytes = (size_t) n * (size_t) (n - 1) / 2 * (size_t) et;
+				int mrc;
+				if((mrc = ccg_malloc(ctx, &A_dev, bytes)) || (mrc = ccg_malloc(ctx, &W_dev, bytes)) ||
+				   (mrc = ccg_memcpy_h2d(ctx, A_dev, D->mat, bytes)) || (mrc = ccg_memcpy_h2d(ctx, W_dev, D->mat, bytes))) {
+					fprintf(stderr, "ccphylo_amd: tree --phycmp: no device copy of the matrix: %s\n", ccg_strerror(mrc));
+					return 1;
+				}
+			}
+		}
 		if(n > 2) {
 			if(jcap < (size_t) n) {
 				jcap = n;
@@ -285,7 +368,8 @@ static int main_tree(int argc, char **argv) {
 				}
 			} else {
 				if(!ctx) ctx = open_gpu(device);
-				rc = ccg_tree(ctx, &ta, D->mat, joins, &nj, &fn, &fd, st);
+				rc = cmp ? ccg_tree_dev(ctx, &ta, W_dev, joins, &nj, &fn, &fd, st)
+				         : ccg_tree(ctx, &ta, D->mat, joins, &nj, &fn, &fd, st);
 			}
 			if(rc) {
 				fprintf(stderr, "ccphylo_amd: tree construction failed: %s\n", ccg_strerror(rc));
@@ -307,9 +391,23 @@ static int main_tree(int argc, char **argv) {
 		t1 = clock();
 		fprintf(stderr, "# Total time used Constructing tree: %.2f s.\n", (double) (t1 - t0) / 1000000);
 		t0 = t1;
+		if(cmp) {
+			fflush(out);   /* the tree is written whatever the comparison says */
+			const int bad = tree_phycmp(ctx, cmp, cmpflag, (char *) T->names[0]->seq, taxa, n, et, A_dev, W_dev);
+			for(int i = 0; i < n; ++i) free(taxa[i]);
+			free(taxa);
+			if(A_dev) ccg_free(ctx, A_dev);
+			if(W_dev) ccg_free(ctx, W_dev);
+			A_dev = W_dev = NULL;
+			if(bad) {
+				err = 1;
+				break;
+			}
+		}
 	}
 	if(out != stdout) fclose(out);
 	else fflush(stdout);
+	if(cmp) fclose(cmp);
 	ccq_close(r);
 	ccq_ltd_free(D);
 	ccq_names_free(T);
@@ -1470,13 +1568,402 @@ static int main_tsv2phy(int argc, char **argv) {
 	return 0;
 }
 
+/* ============================================================ nwck2phy */
+static int nwck2phy_help(FILE *out) {
+	fprintf(out, "#CCPhylo nwck2phy converts newick files to phylip distance files.\n");
+	fprintf(out, "#   %-24s\t%-32s\t%s\n", "Options are:", "Desc:", "Default:");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'i', "input", "Input file", "stdin");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'o', "output", "Output file", "stdout");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'x', "print_precision", "Floating point print precision", "9");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'f', "flag", "Output flags", "1");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'F', "flag_help", "Help on option \"-f\"", "");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'p', "float_precision", "Float precision on distance matrix", "False / double");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 's', "short_precision", "Short precision on distance matrix", "False / double / 1e0");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'b', "byte_precision", "Byte precision on distance matrix", "False / double / 1e0");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'H', "mmap", "Allocate matrix on the disk", "False");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'T', "tmp", "Set directory for temporary files", "");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'h', "help", "Shows this helpmessage", "");
+	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "device", "GPU", "0");
+	return out == stderr;
+}
+
+/* nwck2phy.c:33 newick2phy: every line's split list through ccg_nwck_ltd, printed by ccq_print_phy */
+static int main_nwck2phy(int argc, char **argv) {
+	const char *in = "-", *outname = "-";
+	int flag = 1, precision = 9, et = 8, device = 0;
+	Args A = {argc, 0, argv};
+	for(A.k = 1; A.k < argc; ++A.k) {
+		char *a = argv[A.k];
+		if(a[0] != '-' || a[1] == 0) {
+			in = a;
+			if(A.k + 1 < argc) {
+				fprintf(stderr, "Unexpected non-option argument(s).\n");
+				return 1;
+			}
+			break;
+		}
+		if(a[1] == '-') {
+			char *name = a + 2, *eq = strchr(name, '=');
+			char *att = NULL;
+			if(eq) {
+				*eq = 0;
+				att = eq + 1;
+			}
+			if(*name == 0) { continue; }
+			else if(!strcmp(name, "input")) in = opt_value(&A, att, "input");
+			else if(!strcmp(name, "output")) outname = opt_value(&A, att, "output");
+			else if(!strcmp(name, "print_precision")) precision = (int) opt_num(&A, att, "print_precision");
+			else if(!strcmp(name, "flag")) flag = (int) opt_num(&A, att, "flag");
+			else if(!strcmp(name, "flag_help")) flag = -1;
+			else if(!strcmp(name, "float_precision")) et = 4;
+			else if(!strcmp(name, "short_precision")) { et = 2; (void) opt_dvalue_def(&A, att, 1.0, "short_precision"); }
+			else if(!strcmp(name, "byte_precision")) { et = 1; (void) opt_dvalue_def(&A, att, 1.0, "byte_precision"); }
+			else if(!strcmp(name, "mmap")) { /* host memory knob: no effect on HBM */ }
+			else if(!strcmp(name, "tmp")) (void) opt_value(&A, att, "tmp");
+			else if(!strcmp(name, "device")) device = (int) opt_num(&A, att, "device");
+			else if(!strcmp(name, "help")) return nwck2phy_help(stdout);
+			else die_opt("Unknown", a);
+			continue;
+		}
+		for(char *p = a + 1; *p; ++p) {
+			char o = *p, *att = p + 1;
+			int took = 1;
+			switch(o) {
+				case 'i': in = opt_value(&A, att, "i"); break;
+				case 'o': outname = opt_value(&A, att, "o"); break;
+				case 'x': precision = (int) opt_num(&A, att, "x"); break;
+				case 'f': flag = (int) opt_num(&A, att, "f"); break;
+				case 'T': (void) opt_value(&A, att, "T"); break;
+				case 's': et = 2; (void) opt_dvalue_def(&A, att, 1.0, "s"); break;
+				case 'b': et = 1; (void) opt_dvalue_def(&A, att, 1.0, "b"); break;
+				case 'F': flag = -1; took = 0; break;
+				case 'p': et = 4; took = 0; break;
+				case 'H': took = 0; break;
+				case 'h': return nwck2phy_help(stdout);
+				default: {
+					char bad[3] = {'-', o, 0};
+					die_opt("Unknown", bad);
+				}
+			}
+			if(took) break;
+		}
+	}
+	if(flag == -1) {
+		fprintf(stdout, "Format flags output format, add them to combine them.\n");
+		fprintf(stdout, "#\n");
+		fprintf(stdout, "# 1:\tRelaxed Phylip\n");
+		fprintf(stdout, "#\n");
+		return 0;
+	}
+	if(et == 2 || et == 1) {
+		/* the reference adds separately scaled and rounded encodings there (nwck2phy.c:245): not the path length */
+		fprintf(stderr, "ccphylo_amd: nwck2phy with short / byte precision (-s / -b) is not implemented.\n");
+		return 1;
+	}
+	FILE *out = (outname[0] == '-' && outname[1] == 0) ? stdout : fopen(outname, "wb");
+	if(!out) {
+		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
+		return errno ? errno : 1;
+	}
+	ccq_reader *r = ccq_open(in);
+	if(!r) {
+		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
+		return errno ? errno : 1;
+	}
+	ccg_ctx *ctx = NULL;
+	ccq_ltd *D = ccq_ltd_new(128, et, 1.0);
+	ccq_str *header = ccq_new(64);
+	char *line = NULL, *err = NULL;
+	size_t cap = 0, len;
+	int status = 0;
+	while(ccq_read_nwck(r, &line, &cap, &len)) {
+		char **names = NULL;
+		ccq_split *splits = NULL;
+		int n = 0;
+		err = realloc(err, len + 128);   /* a message quotes the node, which may be most of the line */
+		const int rc = ccq_newick_splits(line, len, header, &names, &splits, &n, err, len + 128);
+		if(rc) {
+			/* rc 1: the reference's own exit and message; -1: where it is undefined */
+			fprintf(stderr, rc > 0 ? "%s\n" : "ccphylo_amd: nwck2phy: %s\n", err);
+			status = 1;
+			break;
+		}
+		ccq_ltd_reserve(D, n);
+		D->n = n;
+		if(n > 1) {
+			if(!ctx) ctx = open_gpu(device);
+			const int grc = ccg_nwck_ltd(ctx, (const ccg_split *) splits, n - 1, et, D->mat);
+			if(grc) {
+				fprintf(stderr, "ccphylo_amd: nwck2phy failed: %s\n", ccg_strerror(grc));
+				return 1;
+			}
+		}
+		ccq_print_phy(out, D, names, NULL, (char *) header->seq, (unsigned) flag | CCQ_PHY_KEEP_DIRS, precision);
+		fflush(out);
+		ccq_newick_splits_free(names, splits, n);
+	}
+	if(out != stdout) fclose(out);
+	else fflush(stdout);
+	ccq_close(r);
+	ccq_ltd_free(D);
+	ccq_free(header);
+	free(line);
+	free(err);
+	if(ctx) ccg_destroy(ctx);
+	return status;
+}
+
+/* ============================================================== phycmp */
+static int phycmp_help(FILE *out) {
+	fprintf(out, "# CCPhylo phycmp compares two distance matrices in phylip format.\n");
+	fprintf(out, "#   %-24s\t%-32s\t%s\n", "Options are:", "Desc:", "Default:");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'i', "input", "Input file(s)", "stdin");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'o', "output", "Output file", "stdout");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'S', "separator", "Separator", "\\t");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'f', "flag", "Output flags", "1");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'F', "flag_help", "Help on option \"-f\"", "");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'p', "float_precision", "Float precision on distance matrix", "False / double");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 's', "short_precision", "Short precision on distance matrix", "False / double / 1e0");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'b', "byte_precision", "Byte precision on distance matrix", "False / double / 1e0");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'H', "mmap", "Allocate matrix on the disk", "False");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'T', "tmp", "Set directory for temporary files", "");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'h', "help", "Shows this helpmessage", "");
+	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "by_name", "Match the second matrix's rows by name", "False");
+	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "device", "GPU", "0");
+	return out == stderr;
+}
+
+typedef struct {
+	const char *name;
+	int row;
+} name_row;
+
+static int name_row_cmp(const void *a, const void *b) {
+	return strcmp(((const name_row *) a)->name, ((const name_row *) b)->name);
+}
+
+/* perm[i] = the row of names2 called names1[i]; 0, or 1 with a message when
+ * the two name sets differ or a name repeats */
+static int perm_by_name(char **names1, char **names2, int n, int32_t *perm, char *msg, size_t msglen) {
+	name_row *t = malloc((size_t) n * sizeof(name_row));
+	int rc = 0;
+	for(int i = 0; i < n; ++i) {
+		t[i].name = names2[i];
+		t[i].row = i;
+	}
+	qsort(t, (size_t) n, sizeof(name_row), name_row_cmp);
+	for(int i = 1; i < n && !rc; ++i) {
+		if(!strcmp(t[i - 1].name, t[i].name)) {
+			snprintf(msg, msglen, "entry \"%s\" repeats", t[i].name);
+			rc = 1;
+		}
+	}
+	unsigned char *used = calloc((size_t) n, 1);
+	for(int i = 0; i < n && !rc; ++i) {
+		name_row key = {names1[i], 0};
+		const name_row *hit = bsearch(&key, t, (size_t) n, sizeof(name_row), name_row_cmp);
+		if(!hit) {
+			snprintf(msg, msglen, "entry \"%s\" is in one matrix only", names1[i]);
+			rc = 1;
+		} else if(used[hit->row]) {
+			snprintf(msg, msglen, "entry \"%s\" repeats", names1[i]);
+			rc = 1;
+		} else {
+			used[hit->row] = 1;
+			perm[i] = hit->row;
+		}
+	}
+	free(used);
+	free(t);
+	return rc;
+}
+
+/* phycmp.c:176 main_phycmp / :56 phyfilecmp: two matrices, one pass of ccg_ltd_cmp */
+static int main_phycmp(int argc, char **argv) {
+	const char *outname = "-", *files[2] = {"-", "-"};
+	int flag = 1, et = 8, device = 0, by_name = 0, nfiles = 0;
+	char sep = '\t';
+	Args A = {argc, 0, argv};
+	for(A.k = 1; A.k < argc; ++A.k) {
+		char *a = argv[A.k];
+		if(a[0] != '-' || a[1] == 0) {
+			/* non-options: the input files (phycmp.c:295) */
+			nfiles = 0;
+			for(; A.k < argc; ++A.k) {
+				if(nfiles < 2) files[nfiles] = argv[A.k];
+				++nfiles;
+			}
+			break;
+		}
+		char *att = NULL, o = 0;
+		int is_input = 0;
+		if(a[1] == '-') {
+			char *name = a + 2, *eq = strchr(name, '=');
+			if(eq) {
+				*eq = 0;
+				att = eq + 1;
+			}
+			if(*name == 0) { continue; }
+			else if(!strcmp(name, "input")) is_input = 1;
+			else if(!strcmp(name, "output")) outname = opt_value(&A, att, "output");
+			else if(!strcmp(name, "separator")) sep = opt_value(&A, att, "separator")[0];
+			else if(!strcmp(name, "flag")) flag = (int) opt_num(&A, att, "flag");
+			else if(!strcmp(name, "flag_help")) flag = -1;
+			else if(!strcmp(name, "float_precision")) et = 4;
+			else if(!strcmp(name, "short_precision")) { et = 2; (void) opt_dvalue_def(&A, att, 1.0, "short_precision"); }
+			else if(!strcmp(name, "byte_precision")) { et = 1; (void) opt_dvalue_def(&A, att, 1.0, "byte_precision"); }
+			else if(!strcmp(name, "mmap")) { /* host memory knob: no effect on HBM */ }
+			else if(!strcmp(name, "tmp")) (void) opt_value(&A, att, "tmp");
+			else if(!strcmp(name, "by_name")) by_name = 1;
+			else if(!strcmp(name, "device")) device = (int) opt_num(&A, att, "device");
+			else if(!strcmp(name, "help")) return phycmp_help(stdout);
+			else die_opt("Unknown", a);
+		} else {
+			for(char *p = a + 1; *p && !is_input; ++p) {
+				int took = 1;
+				o = *p;
+				att = p + 1;
+				switch(o) {
+					case 'i': is_input = 1; break;
+					case 'o': outname = opt_value(&A, att, "o"); break;
+					case 'S': sep = opt_value(&A, att, "S")[0]; break;
+					case 'f': flag = (int) opt_num(&A, att, "f"); break;
+					case 'T': (void) opt_value(&A, att, "T"); break;
+					case 's': et = 2; (void) opt_dvalue_def(&A, att, 1.0, "s"); break;
+					case 'b': et = 1; (void) opt_dvalue_def(&A, att, 1.0, "b"); break;
+					case 'F': flag = -1; took = 0; break;
+					case 'p': et = 4; took = 0; break;
+					case 'H': took = 0; break;
+					case 'h': return phycmp_help(stdout);
+					default: {
+						char bad[3] = {'-', o, 0};
+						die_opt("Unknown", bad);
+					}
+				}
+				if(took) break;
+			}
+		}
+		if(is_input) {
+			/* a list: the attached value or the next word, then every word that is no option (cmdline.c:185, :216) */
+			nfiles = 0;
+			files[nfiles++] = opt_value(&A, att, "input");
+			while(A.k + 1 < argc && (argv[A.k + 1][0] != '-' || argv[A.k + 1][1] == 0)) {
+				++A.k;
+				if(nfiles < 2) files[nfiles] = argv[A.k];
+				++nfiles;
+			}
+		}
+	}
+	if(flag == -1) {
+		fprintf(stdout, "# Distance calculation methods:\n");
+		fprintf(stdout, "#\n");
+		fprintf(stdout, "# 1\tcos: Calculate cosine distance between vectors.\n");
+		fprintf(stdout, "# 2\tchi2: Calculate the chi square distance\n");
+		fprintf(stdout, "# 4\tbc: Calculate the Bray-Curtis dissimilarity between vectors.\n");
+		fprintf(stdout, "# 8\tl1: Calculate distance between vectors as the 1-norm distance between the count vectors.\n");
+		fprintf(stdout, "# 16\tl2: Calculate distance between vectors as the 2-norm distance between the count vectors.\n");
+		fprintf(stdout, "# 32\tlinf: Calculate distance between vectors as the l_infinity distance between the count vectors.\n");
+		fprintf(stdout, "# 64\tp: Calculate Pearsons correlation between vectors.\n");
+		fprintf(stdout, "#\n");
+		return 0;
+	}
+	if(et == 2 || et == 1) {
+		fprintf(stderr, "ccphylo_amd: phycmp with short / byte precision (-s / -b) is not implemented.\n");
+		return 1;
+	}
+	if(nfiles > 2) {
+		fprintf(stderr, "ccphylo_amd: phycmp takes two matrices: two files, or one file that holds both.\n");
+		return 1;
+	}
+	if(nfiles == 0) nfiles = 1;   /* stdin holds both */
+	FILE *out = (outname[0] == '-' && outname[1] == 0) ? stdout : fopen(outname, "wb");
+	if(!out) {
+		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
+		return errno ? errno : 1;
+	}
+	ccq_reader *r = ccq_open(files[0]);
+	if(!r) {
+		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
+		return errno ? errno : 1;
+	}
+	ccq_ltd *D1 = ccq_ltd_new(32, et, 1.0), *D2 = ccq_ltd_new(32, et, 1.0);
+	ccq_names *T1 = ccq_names_new(32, 4), *T2 = ccq_names_new(32, 4);
+	int err = 0;
+	const int n1 = ccq_load_phy(r, D1, T1, sep, 0, &err);
+	if(nfiles != 1) {
+		ccq_close(r);
+		if(!(r = ccq_open(files[1]))) {
+			fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
+			return errno ? errno : 1;
+		}
+	}
+	const int n2 = ccq_load_phy(r, D2, T2, sep, 0, &err);
+	ccq_close(r);
+	/* phycmp.c:96-105 */
+	if(n1 <= 0 || n2 <= 0) {
+		fprintf(stderr, "Missing matrix\n");
+		return 1;
+	} else if(n1 != n2) {
+		fprintf(stderr, "Matrices differ in size.\n");
+		return 1;
+	}
+	const int n = n1;
+	char **nm1 = malloc((size_t) n * sizeof(char *)), **nm2 = malloc((size_t) n * sizeof(char *));
+	for(int i = 0; i < n; ++i) {
+		nm1[i] = (char *) T1->names[i]->seq;
+		nm2[i] = (char *) T2->names[i]->seq;
+	}
+	int32_t *perm = NULL;
+	if(by_name) {
+		char msg[512];
+		perm = malloc((size_t) n * sizeof(int32_t));
+		if(perm_by_name(nm1, nm2, n, perm, msg, sizeof(msg))) {
+			fprintf(stderr, "ccphylo_amd: phycmp --by_name: %s.\n", msg);
+			return 1;
+		}
+	} else {
+		for(int i = 0; i < n; ++i) {
+			if(strcmp(nm1[i], nm2[i])) {
+				fprintf(stderr, "Matrices has different entries.\n");
+				return 1;
+			}
+		}
+	}
+	if(n < 2) {
+		/* the reference reads the first cell of an empty buffer there */
+		fprintf(stderr, "ccphylo_amd: phycmp: a matrix of one entry has no distance to compare.\n");
+		return 1;
+	}
+	ccg_ctx *ctx = open_gpu(device);
+	ccg_cmp_sums sums;
+	const int rc = ccg_ltd_cmp(ctx, D1->mat, D2->mat, n, et, perm, &sums);
+	if(rc) {
+		fprintf(stderr, "ccphylo_amd: phycmp failed: %s\n", ccg_strerror(rc));
+		return 1;
+	}
+	ccq_print_phycmp(out, &sums, (int64_t) n * (n - 1) / 2, flag);
+	if(out != stdout) fclose(out);
+	else fflush(stdout);
+	free(nm1);
+	free(nm2);
+	free(perm);
+	ccq_ltd_free(D1);
+	ccq_ltd_free(D2);
+	ccq_names_free(T1);
+	ccq_names_free(T2);
+	ccg_destroy(ctx);
+	return 0;
+}
+
 static int main_help(FILE *out) {
-	fprintf(out, "# CCPhylo (ccphylo_amd: MI355X engine for dist and tree)\n");
+	fprintf(out, "# CCPhylo (ccphylo_amd: MI355X engine for dist, tree and their matrices)\n");
 	fprintf(out, "# Usage: ccphylo <command> [options]\n");
 	fprintf(out, "#    %-16s\t%s\n", "dist", "all-pairs SNP distances of an MSA (GPU)");
 	fprintf(out, "#    %-16s\t%s\n", "tree", "NJ / DNJ trees from Phylip matrices (GPU)");
 	fprintf(out, "#    %-16s\t%s\n", "dbscan", "DBSCAN clusters from Phylip matrices (GPU)");
 	fprintf(out, "#    %-16s\t%s\n", "tsv2phy", "all-pairs distances of a table's rows (GPU)");
+	fprintf(out, "#    %-16s\t%s\n", "nwck2phy", "path-length matrices of Newick trees (GPU)");
+	fprintf(out, "#    %-16s\t%s\n", "phycmp", "cos, chi2, bc, l1, l2, linf and Pearson of two Phylip matrices (GPU)");
 	return out == stderr;
 }
 
@@ -1489,7 +1976,9 @@ int main(int argc, char **argv) {
 	if(!strcmp(argv[1], "tree")) return main_tree(argc - 1, argv + 1);
 	if(!strcmp(argv[1], "dbscan")) return main_dbscan(argc - 1, argv + 1);
 	if(!strcmp(argv[1], "tsv2phy")) return main_tsv2phy(argc - 1, argv + 1);
+	if(!strcmp(argv[1], "nwck2phy")) return main_nwck2phy(argc - 1, argv + 1);
+	if(!strcmp(argv[1], "phycmp")) return main_phycmp(argc - 1, argv + 1);
 	if(!strcmp(argv[1], "-h") || !strcmp(argv[1], "--help")) return main_help(stdout);
-	fprintf(stderr, "ccphylo_amd: command \"%s\" is outside the GPU engine's scope (dist, tree, dbscan, tsv2phy).\n", argv[1]);
+	fprintf(stderr, "ccphylo_amd: command \"%s\" is outside the GPU engine's scope (dist, tree, dbscan, tsv2phy, nwck2phy, phycmp).\n", argv[1]);
 	return 1;
 }

@@ -520,7 +520,7 @@ static void *print_rows(void *arg) {
 			name[L - 1] = 0;
 			++name;
 		}
-		name = strip_dir(name);
+		if(!(J->format & CCQ_PHY_KEEP_DIRS)) name = strip_dir(name);
 		int k = (J->format & 1) ? snprintf(cell, sizeof(cell), "%s", name) : snprintf(cell, sizeof(cell), "%-10.10s", name);
 		if(k >= (int) sizeof(cell)) {
 			const size_t nl = strlen(name);

@@ -156,6 +156,14 @@ class Coll(C.Structure):
 
 CCG_CTX_NOSYNC = 1
 JOIN_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("Li", np.float64), ("Lj", np.float64)])
+# ccg_split / ccq_split: split s creates row s + 1 from row org
+SPLIT_DTYPE = np.dtype([("org", np.int32), ("Li", np.float64), ("Lj", np.float64)], align=True)
+CMP_SUMS = ("ab", "aa", "bb", "a", "b", "apb", "mn", "l1", "l2", "chi2", "linf")   # ccg_cmp_sums
+CMP_METRICS = ("cos", "chi2", "bc", "l1", "l2", "linf", "p")                        # the bits of `phycmp -f`
+
+
+class CmpSums(C.Structure):
+    _fields_ = [(k, C.c_double) for k in CMP_SUMS]
 
 # every symbol of include/ccphylo_amd.h
 ENGINE_SYMBOLS = [
@@ -169,6 +177,7 @@ ENGINE_SYMBOLS = [
     "ccg_shutdown", "ccg_dbscan", "ccg_dbscan_dev", "ccg_dbscan_count_dev",
     "ccg_vec_ltd", "ccg_vec_ltd_dev", "ccg_last_vec_ms", "ccg_last_vec_plan",
     "ccg_meth_mask", "ccg_meth_mask_dev",
+    "ccg_nwck_ltd", "ccg_nwck_ltd_dev", "ccg_last_nwck", "ccg_ltd_cmp", "ccg_ltd_cmp_dev", "ccg_last_cmp_ms",
 ]
 # every symbol of include/ccphylo_host.h
 HOST_SYMBOLS = [
@@ -180,6 +189,7 @@ HOST_SYMBOLS = [
     "ccq_load_msa", "ccq_load_msa_par", "ccq_msa_free", "ccq_load_fsa_files", "ccq_load_kma", "ccq_kma_free",
     "ccq_print_dbscan", "ccq_load_tsv", "ccq_print_tsvphy",
     "ccq_load_motifs", "ccq_meth_clear_row", "ccq_load_msa_meth", "ccq_load_msa_par_meth", "ccq_msa_meth_finish",
+    "ccq_newick_splits", "ccq_newick_splits_free", "ccq_read_nwck", "ccq_cmp_metric", "ccq_print_phycmp",
 ]
 
 _engine = None
@@ -259,6 +269,13 @@ def engine_lib():
         lib.ccg_last_vec_plan.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         lib.ccg_meth_mask.argtypes = [C.c_void_p, C.POINTER(MethArgs), C.c_void_p, C.POINTER(C.c_int64)]
         lib.ccg_meth_mask_dev.argtypes = lib.ccg_meth_mask.argtypes
+        lib.ccg_nwck_ltd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        lib.ccg_nwck_ltd_dev.argtypes = lib.ccg_nwck_ltd.argtypes
+        lib.ccg_last_nwck.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        lib.ccg_ltd_cmp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                    C.POINTER(CmpSums)]
+        lib.ccg_ltd_cmp_dev.argtypes = lib.ccg_ltd_cmp.argtypes
+        lib.ccg_last_cmp_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         _engine = lib
     return _engine
 
@@ -317,6 +334,17 @@ def host_lib():
                                      C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
         lib.ccq_print_tsvphy.restype = None
         lib.ccq_print_tsvphy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint, C.c_int]
+        lib.ccq_free.restype = None
+        lib.ccq_free.argtypes = [C.c_void_p]
+        lib.ccq_newick_splits.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p),
+                                          C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
+        lib.ccq_read_nwck.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        lib.ccq_newick_splits_free.restype = None
+        lib.ccq_newick_splits_free.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.ccq_cmp_metric.restype = C.c_double
+        lib.ccq_cmp_metric.argtypes = [C.POINTER(CmpSums), C.c_int64, C.c_int]
+        lib.ccq_print_phycmp.restype = None
+        lib.ccq_print_phycmp.argtypes = [C.c_void_p, C.POINTER(CmpSums), C.c_int64, C.c_int]
         _host = lib
     return _host
 
@@ -637,6 +665,56 @@ class Device:
                     "ccg_selftest_row_sum")
         return out.value, bool(par.value)
 
+    def nwck_ltd(self, splits, etype=8):
+        """The path-length LT of a tree from its split list (ccg_nwck_ltd;
+        splits as newick_splits returns them): a packed LT of len(splits) + 1
+        rows, bit for bit the reference's `nwck2phy` matrix."""
+        sp = np.ascontiguousarray(splits, dtype=SPLIT_DTYPE)
+        n = len(sp) + 1
+        D = np.zeros(n * (n - 1) // 2, dtype=ETYPES[etype])
+        self._check(self.lib.ccg_nwck_ltd(self.h, sp.ctypes.data, len(sp), etype, D.ctypes.data), "ccg_nwck_ltd")
+        return D
+
+    def nwck_ltd_dev(self, splits, D_ptr, etype=8):
+        """Same into a device LT of (len(splits) + 1) rows (ccg_nwck_ltd_dev)."""
+        sp = np.ascontiguousarray(splits, dtype=SPLIT_DTYPE)
+        self._check(self.lib.ccg_nwck_ltd_dev(self.h, sp.ctypes.data, len(sp), etype, C.c_void_p(D_ptr)),
+                    "ccg_nwck_ltd_dev")
+
+    def last_nwck(self):
+        """(device ms, kernel launches) of the last replay on this context."""
+        ms, ln = C.c_double(0), C.c_int64(0)
+        self._check(self.lib.ccg_last_nwck(self.h, C.byref(ms), C.byref(ln)), "ccg_last_nwck")
+        return ms.value, ln.value
+
+    def ltd_cmp(self, A, B, n, etype=8, perm=None):
+        """`phycmp` of two packed host LTs (ccg_ltd_cmp); the cell (i, j) of A
+        against B's at rows perm[i], perm[j].  Returns (sums, metrics): dicts
+        over CMP_SUMS and CMP_METRICS."""
+        A = np.ascontiguousarray(A, dtype=ETYPES[etype])
+        B = np.ascontiguousarray(B, dtype=ETYPES[etype])
+        assert A.size == B.size == n * (n - 1) // 2
+        return self._ltd_cmp(self.lib.ccg_ltd_cmp, A.ctypes.data, B.ctypes.data, n, etype, perm)
+
+    def ltd_cmp_dev(self, A_ptr, B_ptr, n, etype=8, perm=None):
+        """Same on device LTs (ccg_ltd_cmp_dev); both are left unmodified."""
+        return self._ltd_cmp(self.lib.ccg_ltd_cmp_dev, A_ptr, B_ptr, n, etype, perm)
+
+    def _ltd_cmp(self, fn_, a, b, n, etype, perm):
+        if perm is not None:
+            perm = np.ascontiguousarray(perm, dtype=np.int32)
+            assert perm.size == n
+        out = CmpSums()
+        rc = fn_(self.h, C.c_void_p(a), C.c_void_p(b), n, etype, perm.ctypes.data if perm is not None else None,
+                 C.byref(out))
+        self._check(rc, "ccg_ltd_cmp")
+        return cmp_close(out, n * (n - 1) // 2)
+
+    def last_cmp_ms(self):
+        ms = C.c_double(0)
+        self._check(self.lib.ccg_last_cmp_ms(self.h, C.byref(ms)), "ccg_last_cmp_ms")
+        return ms.value
+
     # ---- device memory (ccg_malloc & co.) for HBM-resident inputs
     def malloc(self, nbytes):
         p = C.c_void_p()
@@ -943,6 +1021,45 @@ def newick_from_phylip(path, joins_fn, etype=8, byte_scale=1.0, flags=0, precisi
         lib.ccq_ltd_free(D)
         lib.ccq_names_free(T)
     return trees
+
+
+def newick_splits(text):
+    """ccq_newick_splits on one Newick line (str or bytes, without its
+    newline): (header, names, splits) with names the leaf names in row order
+    (bytes) and splits a SPLIT_DTYPE array.  Raises CcgError with the
+    reference's "Invalid limb length at node" message where it exits with it,
+    and with a message naming the node where it is undefined."""
+    if isinstance(text, str):
+        text = text.encode()
+    lib = host_lib()
+    hdr = lib.ccq_new(64)
+    names, sp, n = C.c_void_p(), C.c_void_p(), C.c_int(0)
+    err = C.create_string_buffer(len(text) + 128)   # a message quotes the node, which may be most of the line
+    try:
+        rc = lib.ccq_newick_splits(text, len(text), hdr, C.byref(names), C.byref(sp), C.byref(n), err, len(err))
+        if rc:
+            e = CcgError(err.value.decode("latin-1"))
+            e.code = rc
+            raise e
+        header = C.cast(hdr, C.POINTER(_Str)).contents.seq
+        arr = C.cast(names, C.POINTER(C.c_char_p))
+        out_names = [arr[i] for i in range(n.value)]
+        splits = np.zeros(n.value - 1, dtype=SPLIT_DTYPE)
+        if n.value > 1:
+            C.memmove(splits.ctypes.data, sp, splits.nbytes)
+        lib.ccq_newick_splits_free(names, sp, n)
+        return header or b"", out_names, splits
+    finally:
+        lib.ccq_free(hdr)
+
+
+def cmp_close(sums, cells):
+    """(sums, metrics) dicts from a CmpSums (or a dict over CMP_SUMS) through ccq_cmp_metric."""
+    if isinstance(sums, dict):
+        sums = CmpSums(*[float(sums[k]) for k in CMP_SUMS])
+    lib = host_lib()
+    return ({k: getattr(sums, k) for k in CMP_SUMS},
+            {k: lib.ccq_cmp_metric(C.byref(sums), cells, i) for i, k in enumerate(CMP_METRICS)})
 
 
 def load_motifs(path):

@@ -520,6 +520,68 @@ int ccg_meth_mask(ccg_ctx *ctx, const ccg_meth_args *a, int32_t *inc_count, int6
 int ccg_meth_mask_dev(ccg_ctx *ctx, const ccg_meth_args *a, int32_t *inc_count, int64_t *matches);
 
 /* ------------------------------------------------------------------ */
+/* nwck: the path-length LT of a Newick tree (`nwck2phy`)              */
+/* ------------------------------------------------------------------ */
+/* Replaces the matrix updates of newick2phy (nwck2phy.c:96-225).  The tree
+ * comes as the split list of the host parser ccq_newick_splits: split s finds
+ * m = s + 1 rows and creates row m from row org (0 <= org <= s).  With
+ * c = cell(org, k) read before the split writes, for every k < m:
+ *   cell(m, k)   = Lj for Lj < 0; else Lj + Li for k = org; else c < 0 ? -1 : Lj + c
+ *   cell(org, k) = Li for Li < 0; else c + Li where 0 <= c            (k != org)
+ * A cell is read as its element type, added in double and rounded once at the
+ * store, so the LT equals the reference's bit for bit (which also writes one
+ * cell past each new row; the engine does not). */
+typedef struct {
+	int32_t org;
+	double Li, Lj;
+} ccg_split;
+
+/* splits: host memory.  D: host LT of n(n-1)/2 elements, n = nsplits + 1, of
+ * etype 8 or 4 bytes, overwritten entirely; nsplits = 0 writes nothing.
+ * CCG_EUNSUP (with a message) for etype 2 / 1, where the reference adds
+ * separately scaled encodings that are not the path length; CCG_EINVAL for
+ * any other etype, nsplits < 0 or an org outside 0 .. s. */
+int ccg_nwck_ltd(ccg_ctx *ctx, const ccg_split *splits, int nsplits, int etype, void *D);
+/* The same into a DEVICE LT (the splits stay host memory), with
+ * ccg_tree_dev's conventions: waits for the device first unless
+ * CCG_CTX_NOSYNC, runs on the context's stream, returns after its kernels. */
+int ccg_nwck_ltd_dev(ccg_ctx *ctx, const ccg_split *splits, int nsplits, int etype, void *D_dev);
+/* Device milliseconds (HIP events) and kernel launches of the last replay on
+ * this context: one block runs the splits with up to 1024 rows, every later
+ * split is a launch.  0, 0 when nothing ran. */
+int ccg_last_nwck(ccg_ctx *ctx, double *ms, int64_t *launches);
+
+/* ------------------------------------------------------------------ */
+/* ltd_cmp: the sums of `phycmp` over two packed LTs                   */
+/* ------------------------------------------------------------------ */
+/* Replaces the seven passes of phyfilecmp (phycmp.c:111-138) by one.  With a
+ * a cell of A and b the cell of B: ab = sum a b, aa, bb, a = sum a, b, apb =
+ * sum (a + b), mn = sum min(a, b), l1 = sum |a - b|, l2 = sum (a - b)^2,
+ * chi2 = sum (a - b)^2 / (a + b) over a != b, linf = max |a - b|; float rows
+ * form every term in float before widening, as distcmp.c's *_f functions do.
+ * Missing cells (-1) are plain numbers, as in the reference.  The reference's
+ * serial chains are replaced by one fixed-order reduction: each sum lies
+ * within 1e-13 sum|term| of the exactly rounded sum (linf is exact), and two
+ * runs give identical bits.  ccq_cmp_metric (ccphylo_host.h) closes them. */
+typedef struct {
+	double ab, aa, bb, a, b, apb, mn, l1, l2, chi2, linf;
+} ccg_cmp_sums;
+
+/* A, B: host LTs of n(n-1)/2 elements (n >= 2) of etype 8 or 4, left
+ * unmodified.  perm (host memory, n entries, may be NULL): the cell (i, j) of
+ * A is compared with the cell of B at rows perm[i], perm[j].  CCG_EINVAL for
+ * n < 2, an unknown etype, or a perm that is no permutation of 0 .. n-1;
+ * CCG_EUNSUP for etype 2 / 1. */
+int ccg_ltd_cmp(ccg_ctx *ctx, const void *A, const void *B, int n, int etype, const int32_t *perm,
+                ccg_cmp_sums *out);
+/* The same on DEVICE LTs (32-byte aligned; perm and out stay host memory),
+ * with ccg_tree_dev's conventions. */
+int ccg_ltd_cmp_dev(ccg_ctx *ctx, const void *A_dev, const void *B_dev, int n, int etype, const int32_t *perm,
+                    ccg_cmp_sums *out);
+/* Device milliseconds of the last comparison's two kernels on this context. */
+int ccg_last_cmp_ms(ccg_ctx *ctx, double *ms);
+
+/* ------------------------------------------------------------------ */
 /* device memory helpers (for callers that keep the pipeline in HBM)   */
 /* ------------------------------------------------------------------ */
 int ccg_malloc(ccg_ctx *ctx, void **ptr, size_t bytes);

@@ -17,6 +17,7 @@
 #define CCPHYLO_HOST_H
 #include <stdint.h>
 #include <stdio.h>
+#include "ccphylo_amd.h"   /* ccg_cmp_sums */
 
 #ifdef __cplusplus
 extern "C" {
@@ -78,7 +79,9 @@ int ccq_load_phy(ccq_reader *r, ccq_ltd *D, ccq_names *T, char sep, char quotes,
 
 /* phy.c:59 printphy.  names[i] are C strings (may be modified by the quote
  * strip, as in the reference).  include may be NULL.  format bit 1 =
- * relaxed names, bit 4 = comment line. */
+ * relaxed names, bit 4 = comment line; CCQ_PHY_KEEP_DIRS prints a name with
+ * its directories (nwck2phy.c:424 sets noStripDir), which are cut otherwise. */
+#define CCQ_PHY_KEEP_DIRS 0x100u
 void ccq_print_phy(FILE *out, const ccq_ltd *D, char **names, const unsigned char *include,
                    const char *comment, unsigned format, int precision);
 
@@ -123,6 +126,47 @@ void ccq_replay_newick_strings(ccq_names *T, int n0, const ccq_join *joins, int 
                                int final_n, double final_d, int flags, int precision);
 /* tree.c:95-97: a two-taxon matrix */
 void ccq_newick_pair(ccq_names *T, double d, int precision);
+
+/* ---- Newick -> split list (`nwck2phy`) ---- */
+/* Split s creates row s + 1 from row org: the last sub-node of names[org] is
+ * peeled off with limb Lj, the rest keeps the row with limb Li (layout of
+ * ccg_split, include/ccphylo_amd.h). */
+typedef struct {
+	int32_t org;
+	double Li, Lj;
+} ccq_split;
+
+/* getNwck / getSizeNwck / splitNwck / stripNwck / getLimbNwck (nwck.c:157-359)
+ * under the driver loop of nwck2phy.c:96-161, in O(text + N): `line` holds one
+ * input line without its newline, anything before the first '(' goes to
+ * `header` (may be NULL).  On success returns 0 with *n leaves, their names in
+ * row order as the reference prints them and *n - 1 splits, both malloc'ed
+ * (ccq_newick_splits_free).  Decisions are the reference's, its length
+ * bookkeeping included (a peeled node is kept one byte short until a ':' is
+ * found in it).  Returns 1 with the reference's "Invalid limb length at
+ * node:\t<text>" in err where it exits with that, and -1 with a message naming
+ * the node where the reference is undefined: its limb search would leave the
+ * node's bytes (a one-byte node without ')', e.g. the B of "(A:1,BB)"), a
+ * node's parentheses do not balance, or commas outnumber the nodes. */
+int ccq_newick_splits(const char *line, size_t len, ccq_str *header, char ***names, ccq_split **splits, int *n,
+                      char *err, size_t errlen);
+void ccq_newick_splits_free(char **names, ccq_split *splits, int n);
+/* The next line of a Newick file for ccq_newick_splits, framed as getNwck
+ * (nwck.c:157) frames it: the bytes up to the first '(' (earlier newlines
+ * included) and on to the newline, without it, in *buf (realloc'ed; *cap its
+ * size).  Returns 0 at the end of the input; a last line without a newline is
+ * dropped, as in the reference. */
+int ccq_read_nwck(ccq_reader *r, char **buf, size_t *cap, size_t *len);
+
+/* ---- phycmp ---- */
+/* Closes metric `which` (0 cos, 1 chi2, 2 bc, 3 l1, 4 l2, 5 linf, 6 p: the
+ * bits of `phycmp -f`) from the sums of ccg_ltd_cmp over `cells` cells as
+ * distcmp.c does: cos = 1 - ab / sqrt(aa bb), -1 at a zero norm, < 0 -> 0;
+ * bc = 1 - 2 mn / apb, < 0 -> 0; chi2 and l2 take sqrt; p = (ab - a b / n) /
+ * sqrt((aa - a a / n)(bb - b b / n)), 0 at a zero variance. */
+double ccq_cmp_metric(const ccg_cmp_sums *s, int64_t cells, int which);
+/* phycmp.c:111-138: "cos:\t%f" ... "p:\t%f" for the bits of flag, in that order */
+void ccq_print_phycmp(FILE *out, const ccg_cmp_sums *s, int64_t cells, int flag);
 
 /* ---- FASTA / MSA ---- */
 void ccq_code_table(unsigned flag, unsigned char table[256]);
