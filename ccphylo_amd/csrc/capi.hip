@@ -294,6 +294,13 @@ int ccg_memcpy_d2h(ccg_ctx *c, void *dst, const void *src, size_t bytes) {
 	return CCG_OK;
 }
 
+int ccg_memcpy_d2d(ccg_ctx *c, void *dst, const void *src, size_t bytes) {
+	if(!c) return CCG_EINVAL;
+	CCG_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
+	CCG_CHECK(hipStreamSynchronize(c->stream));
+	return CCG_OK;
+}
+
 int ccg_synchronize(ccg_ctx *c) {
 	if(!c) return CCG_EINVAL;
 	CCG_CHECK(hipStreamSynchronize(c->stream));

@@ -46,6 +46,7 @@ enum ccg_ws_slot {
 	CCG_WS_VEC,       // the vec pre-pass's per-row values
 	CCG_WS_METH,      // the motif masking's counters
 	CCG_WS_FIT,       // the split prefix of the Newick replay; the LT comparison's perm, block partials and sums
+	CCG_WS_MERGE,     // the merge's per-source index tables
 	CCG_WS_COUNT
 };
 
@@ -62,6 +63,8 @@ struct ccg_ctx {
 	float nwck_ms;   // the last Newick replay's kernels (the same events)
 	long long nwck_launches;   // ... and how many there were
 	float cmp_ms;    // the last LT comparison's two kernels
+	float merge_ms;  // the last merge batch's (or close's) kernels
+	int merge_plan;  // ... and the form the batch took (CCG_MERGE_SCATTER / _GATHER; 0: nothing ran)
 	int flags;       // CCG_CTX_* (ccg_ctx_configure)
 	int masked;      // the stream was created with a CU mask (ccg_ctx_configure)
 	int ncu, cus;    // the device's CUs; the CUs the stream may use (0: all)
@@ -218,6 +221,13 @@ template <> struct Elem<1> {
 };
 
 __host__ __device__ __forceinline__ int64_t tri(int64_t i) { return i * (i - 1) / 2; }
+// the row of flat cell index idx of a packed LT: tri(i) <= idx < tri(i + 1)
+__device__ __forceinline__ int64_t ltd_row(int64_t idx) {
+	int64_t i = (int64_t) ((1.0 + sqrt(1.0 + 8.0 * (double) idx)) * 0.5);
+	while(tri(i) > idx) --i;
+	while(tri(i + 1) <= idx) ++i;
+	return i;
+}
 
 // Q criterion exactly as nj.c:227 / dnj.c:103 write it
 __device__ __forceinline__ double qcrit(int Ni, int Nj, double d, double sDi, double sDj) {

@@ -56,14 +56,6 @@ __device__ __forceinline__ void cmp_cell(typename Elem<ET>::T a, typename Elem<E
 	linf = linf < ad ? ad : linf;
 }
 
-// the row of flat cell index idx: tri(i) <= idx < tri(i + 1)
-__device__ __forceinline__ int64_t cmp_row(int64_t idx) {
-	int64_t i = (int64_t) ((1.0 + sqrt(1.0 + 8.0 * (double) idx)) * 0.5);
-	while(tri(i) > idx) --i;
-	while(tri(i + 1) <= idx) ++i;
-	return i;
-}
-
 template <int ET>
 __global__ __launch_bounds__(CMP_BLOCK) void k_ltd_cmp(const typename Elem<ET>::T *__restrict__ A,
                                                       const typename Elem<ET>::T *__restrict__ B, int64_t cells,
@@ -87,7 +79,7 @@ __global__ __launch_bounds__(CMP_BLOCK) void k_ltd_cmp(const typename Elem<ET>::
 				for(int u = 0; u < cnt; ++u) b[u] = B[base + u];
 			}
 		} else {
-			int64_t i = cmp_row(base), j = base - tri(i);
+			int64_t i = ltd_row(base), j = base - tri(i);
 			int pi = perm[i];
 			for(int u = 0; u < cnt; ++u) {
 				const int pj = perm[j];

@@ -1,5 +1,5 @@
 /*
- * main.c -- `ccphylo dist`, `tree`, `dbscan`, `tsv2phy`, `nwck2phy` and `phycmp`, the stable
+ * main.c -- `ccphylo dist`, `tree`, `dbscan`, `tsv2phy`, `nwck2phy`, `phycmp` and `merge`, the stable
  * CLI surface, with the hot path on the GPU engine (include/ccphylo_amd.h).
  *
  * Mirrors ref main.c:99 (dispatch), dist.c:473 main_dist / :42 makeMatrix /
@@ -20,7 +20,8 @@
  * the table's LT to the tree in HBM, and writes the Phylip text only with -o;
  * `tree --phycmp FILE [--phycmp_flag F]` replays each tree's path lengths in
  * HBM and writes the `phycmp` lines of matrix against tree to FILE;
- * `phycmp --by_name` maps the second matrix's rows onto the first's by name.
+ * `phycmp --by_name` maps the second matrix's rows onto the first's by name;
+ * `merge --tree FILE [--tree_method M]` hands the merged LT to the tree in HBM.
  */
 #include <ctype.h>
 #include <errno.h>
@@ -1955,6 +1956,303 @@ static int main_phycmp(int argc, char **argv) {
 	return 0;
 }
 
+/* =============================================================== merge */
+static int merge_help(FILE *out) {
+	fprintf(out, "#CCPhylo merges matrices from a multi Phylip file into one matrix\n");
+	fprintf(out, "#   %-24s\t%-32s\t%s\n", "Options are:", "Desc:", "Default:");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'i', "input", "Input multi phylip distance file", "stdin");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'o', "output", "Output file", "stdout");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'w', "nucleotides_weights", "Weigh distance with this Phylip file", "");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'n', "nucleotide_numbers", "Output number of nucleotides included", "False/None");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'S', "separator", "Separator", "\\t");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'x', "print_precision", "Floating point print precision", "9");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'f', "flag", "Output flags", "1");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'F', "flag_help", "Help on option \"-f\"", "");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'p', "float_precision", "Float precision on distance matrix", "double");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 's', "short_precision", "Short precision on distance matrix", "double / 1e0");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'b', "byte_precision", "Byte precision on distance matrix", "double / 1e0");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'H', "mmap", "Allocate matrix on the disk", "False");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'T', "tmp", "Set directory for temporary files", "");
+	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'h', "help", "Shows this helpmessage", "");
+	return out == stderr;
+}
+
+/* The union's accumulators in HBM and the batch being staged (merge.c:122 /
+ * :309 on the engine): every parsed matrix goes to the device at once and
+ * waits there until CCG_MERGE_MAX_SRC are staged or the input ends. */
+typedef struct {
+	ccg_ctx *ctx;
+	int et;
+	void *dD, *dN;       /* packed LTs of `cap` rows */
+	int cap;
+	ccg_merge_args a;    /* a.nsrc sources staged; a.n_prev the union's rows after the last batch */
+	int32_t *idx[CCG_MERGE_MAX_SRC];
+	double dev_ms;       /* device time of the batches and the close */
+} MergeRun;
+
+static int merge_fail(const char *what, int rc) {
+	fprintf(stderr, "ccphylo_amd: merge failed: %s: %s\n", what, ccg_strerror(rc));
+	return 1;
+}
+
+/* applies the staged batch to a union of n rows */
+static int merge_flush(MergeRun *R, int n) {
+	int rc;
+	if(n > R->cap) {   /* capacity doubling; the packed prefix keeps its place (flat index i(i-1)/2 + j) */
+		const int cap = n > 2 * R->cap ? n : 2 * R->cap;
+		const size_t bytes = (size_t) cap * (size_t) (cap - 1) / 2 * (size_t) R->et;
+		const size_t keep = (size_t) R->a.n_prev * (size_t) (R->a.n_prev ? R->a.n_prev - 1 : 0) / 2 * (size_t) R->et;
+		void *nD = NULL, *nN = NULL;
+		if((rc = ccg_malloc(R->ctx, &nD, bytes)) || (rc = ccg_malloc(R->ctx, &nN, bytes))) return merge_fail("union buffers", rc);
+		if(keep && ((rc = ccg_memcpy_d2d(R->ctx, nD, R->dD, keep)) || (rc = ccg_memcpy_d2d(R->ctx, nN, R->dN, keep))))
+			return merge_fail("union growth", rc);
+		if(R->dD) ccg_free(R->ctx, R->dD);
+		if(R->dN) ccg_free(R->ctx, R->dN);
+		R->dD = nD;
+		R->dN = nN;
+		R->cap = cap;
+	}
+	if((rc = ccg_ltd_merge_dev(R->ctx, &R->a, R->dD, R->dN, n))) return merge_fail("ccg_ltd_merge_dev", rc);
+	double ms = 0;
+	ccg_last_merge_ms(R->ctx, &ms);
+	R->dev_ms += ms;
+	for(int s = 0; s < R->a.nsrc; ++s) {
+		if(R->a.src[s].d) ccg_free(R->ctx, (void *) R->a.src[s].d);
+		if(R->a.src[s].w) ccg_free(R->ctx, (void *) R->a.src[s].w);
+		free(R->idx[s]);
+	}
+	R->a.nsrc = 0;
+	R->a.first = 0;
+	R->a.n_prev = n;
+	return 0;
+}
+
+/* stages one parsed matrix (W NULL: unweighted); idx is taken over */
+static int merge_stage(MergeRun *R, const ccq_ltd *D, const ccq_ltd *W, int32_t *idx, int first, int n_union) {
+	const int s = R->a.nsrc++;
+	ccg_merge_src *S = &R->a.src[s];
+	const size_t bytes = (size_t) D->n * (size_t) (D->n - 1) / 2 * (size_t) R->et;
+	int rc;
+	memset(S, 0, sizeof(*S));
+	S->m = D->n;
+	S->idx = R->idx[s] = idx;
+	if(first) R->a.first = 1;
+	if(bytes) {
+		void *p = NULL;
+		if((rc = ccg_malloc(R->ctx, &p, bytes))) return merge_fail("source buffer", rc);
+		S->d = p;
+		if((rc = ccg_memcpy_h2d(R->ctx, p, D->mat, bytes))) return merge_fail("upload", rc);
+		if(W) {
+			if((rc = ccg_malloc(R->ctx, &p, bytes))) return merge_fail("source buffer", rc);
+			S->w = p;
+			if((rc = ccg_memcpy_h2d(R->ctx, p, W->mat, bytes))) return merge_fail("upload", rc);
+		}
+	}
+	return R->a.nsrc == CCG_MERGE_MAX_SRC ? merge_flush(R, n_union) : 0;
+}
+
+static int main_merge(int argc, char **argv) {
+	const char *in = "-", *outname = NULL, *wname = NULL, *nname = NULL, *treename = NULL, *tmethod = "dnj";
+	int flag = 1, precision = 9, et = 8, device = 0, scaled = 0;
+	char sep = '\t';
+	Args A = {argc, 0, argv};
+	for(A.k = 1; A.k < argc; ++A.k) {
+		char *a = argv[A.k];
+		if(a[0] != '-' || a[1] == 0) {
+			in = a;
+			if(A.k + 1 < argc) {
+				fprintf(stderr, "Too many non-option arguments handed.\n");
+				return 1;
+			}
+			break;
+		}
+		if(a[1] == '-') {
+			char *name = a + 2, *eq = strchr(name, '=');
+			char *att = NULL;
+			if(eq) {
+				*eq = 0;
+				att = eq + 1;
+			}
+			if(*name == 0) { continue; }
+			else if(!strcmp(name, "input")) in = opt_value(&A, att, "input");
+			else if(!strcmp(name, "output")) outname = opt_value(&A, att, "output");
+			else if(!strcmp(name, "separator")) sep = opt_value(&A, att, "separator")[0];
+			else if(!strcmp(name, "print_precision")) precision = (int) opt_num(&A, att, "print_precision");
+			else if(!strcmp(name, "nucleotides_weights")) wname = opt_value(&A, att, "nucleotides_weights");
+			else if(!strcmp(name, "nucleotide_numbers")) nname = opt_value(&A, att, "nucleotide_numbers");
+			else if(!strcmp(name, "flag")) flag = (int) opt_num(&A, att, "flag");
+			else if(!strcmp(name, "flag_help")) flag = -1;
+			else if(!strcmp(name, "float_precision")) et = 4;
+			else if(!strcmp(name, "short_precision")) { scaled = 1; (void) opt_dvalue_def(&A, att, 1.0, "short_precision"); }
+			else if(!strcmp(name, "byte_precision")) { scaled = 1; (void) opt_dvalue_def(&A, att, 1.0, "byte_precision"); }
+			else if(!strcmp(name, "mmap")) { /* host memory knob: no effect on HBM */ }
+			else if(!strcmp(name, "tmp")) (void) opt_value(&A, att, "tmp");
+			else if(!strcmp(name, "tree")) treename = opt_value(&A, att, "tree");
+			else if(!strcmp(name, "tree_method")) tmethod = opt_value(&A, att, "tree_method");
+			else if(!strcmp(name, "device")) device = (int) opt_num(&A, att, "device");
+			else if(!strcmp(name, "help")) return merge_help(stdout);
+			else {
+				fprintf(stderr, "Unknown argument or option: \"%s\"\n", a);
+				return 1;
+			}
+			continue;
+		}
+		for(char *p = a + 1; *p; ++p) {
+			char o = *p, *att = p + 1;
+			int took = 1;
+			switch(o) {
+				case 'i': in = opt_value(&A, att, "i"); break;
+				case 'o': outname = opt_value(&A, att, "o"); break;
+				case 'S': sep = opt_value(&A, att, "S")[0]; break;
+				case 'x': precision = (int) opt_num(&A, att, "x"); break;
+				case 'w': wname = opt_value(&A, att, "w"); break;
+				case 'n': nname = opt_value(&A, att, "n"); break;
+				case 'f': flag = (int) opt_num(&A, att, "f"); break;
+				case 'T': (void) opt_value(&A, att, "T"); break;
+				case 's': scaled = 1; (void) opt_dvalue_def(&A, att, 1.0, "s"); break;
+				case 'b': scaled = 1; (void) opt_dvalue_def(&A, att, 1.0, "b"); break;
+				case 'F': flag = -1; took = 0; break;
+				case 'p': et = 4; took = 0; break;
+				case 'H': break;
+				case 'h': return merge_help(stdout);
+				default: {
+					fprintf(stderr, "Unknown argument or option: \"-%c\"\n", o);
+					return 1;
+				}
+			}
+			if(took) break;
+		}
+	}
+	if(flag == -1) {
+		fprintf(stdout, "# Format flags output, add them to combine them.\n");
+		fprintf(stdout, "#\n");
+		fprintf(stdout, "#   1:\tRelaxed Phylip\n");
+		fprintf(stdout, "#   2:\tDistances are pairwise, always true on *.mat files\n");
+		fprintf(stdout, "#   4:\tInclude template name in phylip file\n");
+		fprintf(stdout, "#   8:\tInclude insignificant bases in distance calculation, only affects fasta input\n");
+		fprintf(stdout, "#  16:\tInclude reference, only affects fasta input\n");
+		fprintf(stdout, "#  32:\tDistances based on fasta input\n");
+		fprintf(stdout, "#\n");
+		return 0;
+	}
+	if(scaled) {
+		/* merge.c:163-174 multiplies the scaled integers of d and w without unscaling them, and its
+		 * sums wrap: there is nothing to be compatible with */
+		fprintf(stderr, "ccphylo_amd: merge -s / -b is not supported: the reference multiplies the scaled integers of distance and weight without unscaling them; use double or -p.\n");
+		return 1;
+	}
+	const int tm = treename ? fused_tree_method(tmethod) : 0;
+	if(tm < 0) return 1;
+	ccq_reader *r = ccq_open(in), *rw = wname ? ccq_open(wname) : NULL;
+	if(!r || (wname && !rw)) {
+		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
+		return errno ? errno : 1;
+	}
+	MergeRun R;
+	memset(&R, 0, sizeof(R));
+	R.ctx = open_gpu(device);
+	R.et = R.a.etype = et;
+	R.a.weighted = wname != NULL;
+	ccq_ltd *Dh = ccq_ltd_new(64, et, 1.0), *Wh = wname ? ccq_ltd_new(64, et, 1.0) : NULL;
+	ccq_names *T = ccq_names_new(64, 32);
+	ccq_namemap *M = ccq_namemap_new();
+	int err = 0;
+	for(int mat = 0;; ++mat) {
+		const int m = ccq_load_phy(r, Dh, T, sep, 0, &err);
+		if(mat && !m) break;   /* a size of 0 or the end of the file ends the input (merge.c:183) */
+		/* the weights' names overwrite the distances' (merge.c:144 / :184) */
+		if(Wh && ccq_load_phy(rw, Wh, T, sep, 0, &err) != m) {
+			fprintf(stderr, "Distance and included nucleotides does not concur!\n");
+			return 1;
+		}
+		if(!m) continue;   /* an empty first matrix: the reference reads on */
+		int32_t *idx = malloc((size_t) m * sizeof(int32_t));
+		int ra = 0, rb = 0;
+		if(!idx) {
+			fprintf(stderr, "Error: out of host memory\n");
+			return 12;
+		}
+		if(ccq_merge_index(M, T, m, idx, &ra, &rb)) {
+			/* the reference then updates cell (k, k) of the union, which lies outside row k */
+			fprintf(stderr, "ccphylo_amd: merge: matrix %d holds the name \"%s\" twice, on rows %d and %d.\n", mat + 1,
+			        (char *) T->names[rb]->seq, ra + 1, rb + 1);
+			return 1;
+		}
+		Dh->n = m;
+		if(merge_stage(&R, Dh, Wh, idx, mat == 0, ccq_namemap_n(M))) return 1;
+	}
+	ccq_close(r);
+	if(rw) ccq_close(rw);
+	const int n = ccq_namemap_n(M);
+	if(treename && n < 3) {
+		fprintf(stderr, "ccphylo_amd: --tree needs at least 3 entries (%d).\n", n);
+		return 1;
+	}
+	if(R.a.nsrc && merge_flush(&R, n)) return 1;
+	/* with --tree the Phylip texts are written only where -o / -n ask for them */
+	if(!outname && !treename) outname = "-";
+	if(wname && !nname && !treename) nname = "-";
+	if(!wname) nname = NULL;
+	const size_t cells = (size_t) n * (size_t) (n ? n - 1 : 0) / 2;
+	ccq_ltd *Do = ccq_ltd_new(n > 1 ? n : 2, et, 1.0), *No = nname ? ccq_ltd_new(n > 1 ? n : 2, et, 1.0) : NULL;
+	ccg_join *joins = treename ? malloc((size_t) n * sizeof(ccg_join)) : NULL;
+	int nj = 0, fn = 0, rc = 0;
+	double fd = 0;
+	Do->n = n;
+	if(No) No->n = n;
+	if(cells) {
+		double ms = 0;
+		ccg_tree_args ta = {n, et, 1.0, tm, 0, 1, 0, 0};
+		if((rc = ccg_ltd_merge_close_dev(R.ctx, R.dD, R.dN, n, et))) return merge_fail("ccg_ltd_merge_close_dev", rc);
+		ccg_last_merge_ms(R.ctx, &ms);
+		R.dev_ms += ms;
+		if(outname && (rc = ccg_memcpy_d2h(R.ctx, Do->mat, R.dD, cells * (size_t) et))) return merge_fail("read back", rc);
+		if(No && (rc = ccg_memcpy_d2h(R.ctx, No->mat, R.dN, cells * (size_t) et))) return merge_fail("read back", rc);
+		/* the tree of `merge | tree`: cells as the Phylip text would round them, then the engine, which consumes D */
+		if(treename && (rc = ccg_round_decimal_dev(R.ctx, R.dD, (int64_t) cells, et, precision)))
+			return merge_fail("ccg_round_decimal_dev", rc);
+		if(treename && (rc = ccg_tree_dev(R.ctx, &ta, R.dD, joins, &nj, &fn, &fd, NULL))) return merge_fail("ccg_tree_dev", rc);
+	}
+	if(R.dD) ccg_free(R.ctx, R.dD);
+	if(R.dN) ccg_free(R.ctx, R.dN);
+	ccg_destroy(R.ctx);
+	if(getenv("CCPHYLO_MERGE_TIMES")) fprintf(stderr, "# merge: %.3f ms on the device\n", R.dev_ms);
+	char **names = malloc(((size_t) n + 1) * sizeof(char *));
+	for(int i = 0; i < n; ++i) names[i] = strdup(ccq_namemap_name(M, i));
+	FILE *out = NULL, *nout = NULL, *tout = NULL;
+	if(outname) out = (outname[0] == '-' && outname[1] == 0) ? stdout : fopen(outname, "wb");
+	if(nname) nout = (nname[0] == '-' && nname[1] == 0) ? stdout : fopen(nname, "wb");
+	if(treename) tout = (treename[0] == '-' && treename[1] == 0) ? stdout : fopen(treename, "wb");
+	if((outname && !out) || (nname && !nout) || (treename && !tout)) {
+		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
+		return errno ? errno : 1;
+	}
+	if(treename) {   /* the names `merge | tree` would hold, taken before the writer strips quotes */
+		ccq_names *Tt = ccq_names_new(32, 4);   /* as tree.c:61-66 */
+		ccq_names_set(Tt, names, n, (unsigned) flag, '\t');
+		fused_write_newick(tout, Tt, n, joins, nj, fn, fd, 0, precision);
+		fflush(stdout);
+		ccq_names_free(Tt);
+	}
+	if(out) ccq_print_phy(out, Do, names, NULL, "Merged", (unsigned) flag, precision);
+	if(nout) {
+		ccq_print_phy(nout, No, names, NULL, "Merged", (unsigned) flag, precision);
+		if(nout != stdout) fclose(nout);
+	}
+	if(out && out != stdout) fclose(out);
+	fflush(stdout);
+	for(int i = 0; i < n; ++i) free(names[i]);
+	free(names);
+	free(joins);
+	ccq_ltd_free(Do);
+	if(No) ccq_ltd_free(No);
+	ccq_ltd_free(Dh);
+	if(Wh) ccq_ltd_free(Wh);
+	ccq_names_free(T);
+	ccq_namemap_free(M);
+	return 0;
+}
+
 static int main_help(FILE *out) {
 	fprintf(out, "# CCPhylo (ccphylo_amd: MI355X engine for dist, tree and their matrices)\n");
 	fprintf(out, "# Usage: ccphylo <command> [options]\n");
@@ -1964,6 +2262,7 @@ static int main_help(FILE *out) {
 	fprintf(out, "#    %-16s\t%s\n", "tsv2phy", "all-pairs distances of a table's rows (GPU)");
 	fprintf(out, "#    %-16s\t%s\n", "nwck2phy", "path-length matrices of Newick trees (GPU)");
 	fprintf(out, "#    %-16s\t%s\n", "phycmp", "cos, chi2, bc, l1, l2, linf and Pearson of two Phylip matrices (GPU)");
+	fprintf(out, "#    %-16s\t%s\n", "merge", "the matrices of a multi Phylip file into one (GPU)");
 	return out == stderr;
 }
 
@@ -1978,7 +2277,8 @@ int main(int argc, char **argv) {
 	if(!strcmp(argv[1], "tsv2phy")) return main_tsv2phy(argc - 1, argv + 1);
 	if(!strcmp(argv[1], "nwck2phy")) return main_nwck2phy(argc - 1, argv + 1);
 	if(!strcmp(argv[1], "phycmp")) return main_phycmp(argc - 1, argv + 1);
+	if(!strcmp(argv[1], "merge")) return main_merge(argc - 1, argv + 1);
 	if(!strcmp(argv[1], "-h") || !strcmp(argv[1], "--help")) return main_help(stdout);
-	fprintf(stderr, "ccphylo_amd: command \"%s\" is outside the GPU engine's scope (dist, tree, dbscan, tsv2phy, nwck2phy, phycmp).\n", argv[1]);
+	fprintf(stderr, "ccphylo_amd: command \"%s\" is outside the GPU engine's scope (dist, tree, dbscan, tsv2phy, nwck2phy, phycmp, merge).\n", argv[1]);
 	return 1;
 }

@@ -165,6 +165,19 @@ CMP_METRICS = ("cos", "chi2", "bc", "l1", "l2", "linf", "p")                    
 class CmpSums(C.Structure):
     _fields_ = [(k, C.c_double) for k in CMP_SUMS]
 
+MERGE_MAX_SRC = 16       # CCG_MERGE_MAX_SRC
+MERGE_SCATTER, MERGE_GATHER = 1, 2
+
+
+class MergeSrc(C.Structure):
+    _fields_ = [("d", C.c_void_p), ("w", C.c_void_p), ("m", C.c_int), ("idx", C.c_void_p)]
+
+
+class MergeArgs(C.Structure):
+    _fields_ = [("etype", C.c_int), ("weighted", C.c_int), ("first", C.c_int), ("plan", C.c_int), ("nsrc", C.c_int),
+                ("n_prev", C.c_int), ("src", MergeSrc * MERGE_MAX_SRC)]
+
+
 # every symbol of include/ccphylo_amd.h
 ENGINE_SYMBOLS = [
     "ccg_init", "ccg_device_count", "ccg_destroy", "ccg_strerror", "ccg_device_info",
@@ -178,6 +191,8 @@ ENGINE_SYMBOLS = [
     "ccg_vec_ltd", "ccg_vec_ltd_dev", "ccg_last_vec_ms", "ccg_last_vec_plan",
     "ccg_meth_mask", "ccg_meth_mask_dev",
     "ccg_nwck_ltd", "ccg_nwck_ltd_dev", "ccg_last_nwck", "ccg_ltd_cmp", "ccg_ltd_cmp_dev", "ccg_last_cmp_ms",
+    "ccg_ltd_merge", "ccg_ltd_merge_dev", "ccg_ltd_merge_close", "ccg_ltd_merge_close_dev", "ccg_last_merge_ms",
+    "ccg_last_merge_plan", "ccg_memcpy_d2d",
 ]
 # every symbol of include/ccphylo_host.h
 HOST_SYMBOLS = [
@@ -190,6 +205,7 @@ HOST_SYMBOLS = [
     "ccq_print_dbscan", "ccq_load_tsv", "ccq_print_tsvphy",
     "ccq_load_motifs", "ccq_meth_clear_row", "ccq_load_msa_meth", "ccq_load_msa_par_meth", "ccq_msa_meth_finish",
     "ccq_newick_splits", "ccq_newick_splits_free", "ccq_read_nwck", "ccq_cmp_metric", "ccq_print_phycmp",
+    "ccq_namemap_new", "ccq_namemap_free", "ccq_namemap_add", "ccq_namemap_n", "ccq_namemap_name", "ccq_merge_index",
 ]
 
 _engine = None
@@ -276,6 +292,13 @@ def engine_lib():
                                     C.POINTER(CmpSums)]
         lib.ccg_ltd_cmp_dev.argtypes = lib.ccg_ltd_cmp.argtypes
         lib.ccg_last_cmp_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        lib.ccg_ltd_merge.argtypes = [C.c_void_p, C.POINTER(MergeArgs), C.c_void_p, C.c_void_p, C.c_int]
+        lib.ccg_ltd_merge_dev.argtypes = lib.ccg_ltd_merge.argtypes
+        lib.ccg_ltd_merge_close.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        lib.ccg_ltd_merge_close_dev.argtypes = lib.ccg_ltd_merge_close.argtypes
+        lib.ccg_last_merge_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        lib.ccg_last_merge_plan.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        lib.ccg_memcpy_d2d.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         _engine = lib
     return _engine
 
@@ -345,6 +368,16 @@ def host_lib():
         lib.ccq_cmp_metric.argtypes = [C.POINTER(CmpSums), C.c_int64, C.c_int]
         lib.ccq_print_phycmp.restype = None
         lib.ccq_print_phycmp.argtypes = [C.c_void_p, C.POINTER(CmpSums), C.c_int64, C.c_int]
+        lib.ccq_namemap_new.restype = C.c_void_p
+        lib.ccq_namemap_new.argtypes = []
+        lib.ccq_namemap_free.restype = None
+        lib.ccq_namemap_free.argtypes = [C.c_void_p]
+        lib.ccq_namemap_add.argtypes = [C.c_void_p, C.c_char_p]
+        lib.ccq_namemap_n.argtypes = [C.c_void_p]
+        lib.ccq_namemap_name.restype = C.c_char_p
+        lib.ccq_namemap_name.argtypes = [C.c_void_p, C.c_int]
+        lib.ccq_merge_index.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int),
+                                        C.POINTER(C.c_int)]
         _host = lib
     return _host
 
@@ -715,6 +748,59 @@ class Device:
         self._check(self.lib.ccg_last_cmp_ms(self.h, C.byref(ms)), "ccg_last_cmp_ms")
         return ms.value
 
+    def ltd_merge(self, D, N, n, sources, n_prev, etype=8, weighted=True, first=False, plan=0):
+        """One `merge` batch on host arrays (ccg_ltd_merge).  D, N: the union's
+        packed accumulators of n rows, contiguous arrays of the element type,
+        updated in place (rows n_prev .. n-1 are zero-filled first).  sources:
+        up to MERGE_MAX_SRC tuples (d, w, idx) in file order -- packed LTs of
+        len(idx) rows (w None when unweighted) and their distinct union rows."""
+        dt = ETYPES[etype] if etype in (8, 4) else D.dtype   # the engine answers an unsupported etype itself
+        assert D.flags.c_contiguous and N.flags.c_contiguous and D.dtype == N.dtype == dt
+        assert D.size >= n * (n - 1) // 2 and N.size >= n * (n - 1) // 2
+        keep = []
+        srcs = []
+        for d, w, idx in sources:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+            d = np.ascontiguousarray(d, dtype=dt)
+            w = np.ascontiguousarray(w, dtype=dt) if weighted else None
+            keep += [idx, d, w]
+            srcs.append((d.ctypes.data, w.ctypes.data if w is not None else None, idx))
+        self._ltd_merge(self.lib.ccg_ltd_merge, D.ctypes.data, N.ctypes.data, n, srcs, n_prev, etype, weighted, first,
+                        plan)
+
+    def ltd_merge_dev(self, D_ptr, N_ptr, n, sources, n_prev, etype=8, weighted=True, first=False, plan=0):
+        """Same on device accumulators (ccg_ltd_merge_dev): sources are tuples
+        (d_ptr, w_ptr or None, idx), the pointers device memory aligned to 32
+        bytes, idx a host sequence."""
+        srcs = [(d, w, np.ascontiguousarray(idx, dtype=np.int32)) for d, w, idx in sources]
+        self._ltd_merge(self.lib.ccg_ltd_merge_dev, D_ptr, N_ptr, n, srcs, n_prev, etype, weighted, first, plan)
+
+    def _ltd_merge(self, fn_, D_ptr, N_ptr, n, srcs, n_prev, etype, weighted, first, plan):
+        a = MergeArgs(etype=etype, weighted=int(weighted), first=int(first), plan=plan, nsrc=len(srcs), n_prev=n_prev)
+        for s, (d, w, idx) in enumerate(srcs[:MERGE_MAX_SRC]):   # a longer list is the engine's to refuse
+            a.src[s] = MergeSrc(d, w, len(idx), idx.ctypes.data)
+        self._check(fn_(self.h, C.byref(a), C.c_void_p(D_ptr), C.c_void_p(N_ptr), n), "ccg_ltd_merge")
+
+    def ltd_merge_close(self, D, N, n, etype=8):
+        """D = N != 0 ? D / N : -1 over the n rows of host accumulators, in place (ccg_ltd_merge_close)."""
+        assert D.flags.c_contiguous and N.flags.c_contiguous
+        self._check(self.lib.ccg_ltd_merge_close(self.h, D.ctypes.data, N.ctypes.data, n, etype), "ccg_ltd_merge_close")
+
+    def ltd_merge_close_dev(self, D_ptr, N_ptr, n, etype=8):
+        self._check(self.lib.ccg_ltd_merge_close_dev(self.h, C.c_void_p(D_ptr), C.c_void_p(N_ptr), n, etype),
+                    "ccg_ltd_merge_close_dev")
+
+    def last_merge_ms(self):
+        ms = C.c_double(0)
+        self._check(self.lib.ccg_last_merge_ms(self.h, C.byref(ms)), "ccg_last_merge_ms")
+        return ms.value
+
+    def last_merge_plan(self):
+        """The form the last batch took: MERGE_SCATTER, MERGE_GATHER, or 0 where no source had a cell."""
+        plan = C.c_int(0)
+        self._check(self.lib.ccg_last_merge_plan(self.h, C.byref(plan)), "ccg_last_merge_plan")
+        return plan.value
+
     # ---- device memory (ccg_malloc & co.) for HBM-resident inputs
     def malloc(self, nbytes):
         p = C.c_void_p()
@@ -730,6 +816,9 @@ class Device:
 
     def d2h(self, arr, src):
         self._check(self.lib.ccg_memcpy_d2h(self.h, arr.ctypes.data, C.c_void_p(src), arr.nbytes), "d2h")
+
+    def d2d(self, dst, src, nbytes):
+        self._check(self.lib.ccg_memcpy_d2d(self.h, C.c_void_p(dst), C.c_void_p(src), nbytes), "d2d")
 
     def sync(self):
         self._check(self.lib.ccg_synchronize(self.h), "ccg_synchronize")
@@ -981,6 +1070,38 @@ def load_phylip(path, etype=8, byte_scale=1.0, sep="\t", quotes=""):
         lib.ccq_ltd_free(D)
         lib.ccq_names_free(T)
     return out
+
+
+def merge_indices(path, sep="\t"):
+    """The name bookkeeping of `merge` over a multi-Phylip file (ccq_namemap,
+    ccq_merge_index): (union names in insertion order, one int32 index vector
+    per matrix, in the order load_phylip returns them).  Raises CcgError for
+    a matrix that holds a name twice."""
+    lib = host_lib()
+    r = lib.ccq_open(path.encode())
+    if not r:
+        raise FileNotFoundError(path)
+    D = lib.ccq_ltd_new(32, 8, 1.0)
+    T = lib.ccq_names_new(32, 4)
+    M = lib.ccq_namemap_new()
+    err, ra, rb = C.c_int(0), C.c_int(0), C.c_int(0)
+    out = []
+    try:
+        while True:
+            n = lib.ccq_load_phy(r, D, T, sep.encode(), b"\0", C.byref(err))
+            if n <= 0:
+                break
+            idx = np.zeros(n, dtype=np.int32)
+            if lib.ccq_merge_index(M, T, n, idx.ctypes.data, C.byref(ra), C.byref(rb)):
+                raise CcgError(f"matrix {len(out) + 1} holds one name on rows {ra.value + 1} and {rb.value + 1}")
+            out.append(idx)
+        names = [lib.ccq_namemap_name(M, k).decode() for k in range(lib.ccq_namemap_n(M))]
+    finally:
+        lib.ccq_close(r)
+        lib.ccq_ltd_free(D)
+        lib.ccq_names_free(T)
+        lib.ccq_namemap_free(M)
+    return names, out
 
 
 def newick_from_phylip(path, joins_fn, etype=8, byte_scale=1.0, flags=0, precision=9):

@@ -582,12 +582,85 @@ int ccg_ltd_cmp_dev(ccg_ctx *ctx, const void *A_dev, const void *B_dev, int n, i
 int ccg_last_cmp_ms(ccg_ctx *ctx, double *ms);
 
 /* ------------------------------------------------------------------ */
+/* ltd_merge: the matrices of a multi-Phylip file into one (`merge`)   */
+/* ------------------------------------------------------------------ */
+/* Replaces the cell loops of merge (merge.c:122) and jl_merge (merge.c:309).
+ * The union's accumulators D (weighted distance sums) and N (weights) are
+ * packed LTs of the union's rows; a source matrix has m rows and m distinct
+ * union indices idx[0 .. m).  Source cell (i, j) of d (and w) goes to the
+ * union cell of rows idx[i], idx[j], the larger as the row:
+ *   weighted:    D = D + d * w   N = N + w     (the product rounded, then the sum)
+ *   unweighted:  D = D + d       N = N + 1
+ * in the element type (float rows multiply and add in float), the sources of
+ * a batch in order, batches in call order: the reference's chain per cell.
+ * With `first`, source 0 stores d * w (or d) and w (or 1) into its cells
+ * instead of adding, as the reference's first matrix does; a cell a later
+ * matrix creates is +0 + x.  A union cell is touched at most once per source.
+ * Two forms give the same bits: CCG_MERGE_GATHER walks the union's cells of
+ * rows [0, n) once per batch and fetches each source's cell through an inverse
+ * index table; CCG_MERGE_SCATTER walks each source's cells and updates the
+ * union cells in place, one launch per source.  plan 0 takes the gather form
+ * where the batch's source cells are at least 0.13 of the union's cells
+ * (MRG_CROSSOVER in csrc/merge.hip, measured: DESIGN.md 4 "merge",
+ * profiles/merge_bench.json). */
+#define CCG_MERGE_MAX_SRC 16
+#define CCG_MERGE_SCATTER 1
+#define CCG_MERGE_GATHER 2
+typedef struct {
+	const void *d;         /* packed LT, m(m-1)/2 elements of etype bytes */
+	const void *w;         /* the weights' LT (weighted), else ignored */
+	int m;                 /* rows, >= 1 (a one-row source has no cell) */
+	const int32_t *idx;    /* m distinct union indices in [0, n): host memory in both forms */
+} ccg_merge_src;
+
+typedef struct {
+	int etype;             /* 8 double, 4 float */
+	int weighted;          /* 1: d * w and w; 0: d and 1 */
+	int first;             /* 1: source 0 initialises its cells */
+	int plan;              /* 0 auto, CCG_MERGE_SCATTER, CCG_MERGE_GATHER */
+	int nsrc;              /* 1 .. CCG_MERGE_MAX_SRC */
+	int n_prev;            /* the union's rows before this batch, 0 <= n_prev <= n */
+	ccg_merge_src src[CCG_MERGE_MAX_SRC];
+} ccg_merge_args;
+
+/* One batch into the DEVICE accumulators D_dev and N_dev (32-byte aligned, as
+ * the sources' d and w, which are device memory too); n is the union's row
+ * count after the batch.  The caller owns D and N and sizes them for n rows or
+ * more; the packed index of a cell does not depend on n, so a union grows by
+ * appending rows.  The call zero-fills the cells of rows [n_prev, n) before it
+ * adds, so a caller only ever passes the row count of the previous batch (0
+ * with the first).  ccg_tree_dev's conventions: waits for the device first
+ * unless CCG_CTX_NOSYNC, runs on the context's stream, returns after its
+ * kernels.  CCG_EINVAL (with a message, D and N untouched) for nsrc outside
+ * 1 .. CCG_MERGE_MAX_SRC, an index outside [0, n) or repeated within a
+ * source, n_prev outside [0, n], an unknown etype or plan; CCG_EUNSUP for
+ * etype 2 / 1, whose scaled integers the reference multiplies unscaled. */
+int ccg_ltd_merge_dev(ccg_ctx *ctx, const ccg_merge_args *a, void *D_dev, void *N_dev, int n);
+/* The same with HOST sources and HOST accumulators D, N of n rows: rows
+ * [0, n_prev) are uploaded, the batch applied, rows [0, n) written back.  Every
+ * source is uploaded whole (the gather form reads it at random). */
+int ccg_ltd_merge(ccg_ctx *ctx, const ccg_merge_args *a, void *D, void *N, int n);
+/* normalize_ltdMatrix (merge.c:47): D = N != 0 ? D / N : -1 over the cells of n
+ * rows, the division correctly rounded in the element type; N is left as it
+ * is (`merge -n` prints it). */
+int ccg_ltd_merge_close_dev(ccg_ctx *ctx, void *D_dev, const void *N_dev, int n, int etype);
+int ccg_ltd_merge_close(ccg_ctx *ctx, void *D, const void *N, int n, int etype);
+/* Device milliseconds (HIP events) of the last batch's or close's kernels on
+ * this context, the zero fill included. */
+int ccg_last_merge_ms(ccg_ctx *ctx, double *ms);
+/* The form the last batch took: CCG_MERGE_SCATTER or CCG_MERGE_GATHER (0
+ * where no source had a cell). */
+int ccg_last_merge_plan(ccg_ctx *ctx, int *plan);
+
+/* ------------------------------------------------------------------ */
 /* device memory helpers (for callers that keep the pipeline in HBM)   */
 /* ------------------------------------------------------------------ */
 int ccg_malloc(ccg_ctx *ctx, void **ptr, size_t bytes);
 int ccg_free(ccg_ctx *ctx, void *ptr);
 int ccg_memcpy_h2d(ccg_ctx *ctx, void *dst, const void *src, size_t bytes);
 int ccg_memcpy_d2h(ccg_ctx *ctx, void *dst, const void *src, size_t bytes);
+/* device to device, non-overlapping (the merge driver moves the union's packed prefix when it grows) */
+int ccg_memcpy_d2d(ccg_ctx *ctx, void *dst, const void *src, size_t bytes);
 int ccg_synchronize(ccg_ctx *ctx);
 
 /* ------------------------------------------------------------------ */

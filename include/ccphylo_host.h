@@ -168,6 +168,25 @@ double ccq_cmp_metric(const ccg_cmp_sums *s, int64_t cells, int which);
 /* phycmp.c:111-138: "cos:\t%f" ... "p:\t%f" for the bits of flag, in that order */
 void ccq_print_phycmp(FILE *out, const ccg_cmp_sums *s, int64_t cells, int flag);
 
+/* ---- merge ---- */
+/* The name -> union index map of `merge` (merge.c:33 syncMatrices): a name
+ * gets the next index at its first appearance, and the union lists its names
+ * in that order.  Correct at any size, where the reference's table can
+ * register a name twice from the 127th name on (hashmapstrindex.c:30-48). */
+typedef struct ccq_namemap ccq_namemap;
+ccq_namemap *ccq_namemap_new(void);
+void ccq_namemap_free(ccq_namemap *M);
+/* the index of `name` (copied), new or known */
+int ccq_namemap_add(ccq_namemap *M, const char *name);
+int ccq_namemap_n(const ccq_namemap *M);
+/* name i as stored (owned by the map); NULL outside 0 .. n-1 */
+const char *ccq_namemap_name(const ccq_namemap *M, int i);
+/* The index vector of one loaded matrix: idx[r] = the union index of
+ * T->names[r], r < m, new names appended to the map.  Returns 0, or -1 with
+ * *row_a < *row_b the two rows that carry one name (the reference would then
+ * update a cell outside the LT); names before row_b stay registered. */
+int ccq_merge_index(ccq_namemap *M, const ccq_names *T, int m, int32_t *idx, int *row_a, int *row_b);
+
 /* ---- FASTA / MSA ---- */
 void ccq_code_table(unsigned flag, unsigned char table[256]);
 /* seqparse.c:28 FileBuffgetFsa: header (with '>') and codes (< 8 kept) */
