@@ -6,6 +6,7 @@
 // tree_shard_dnj.hip launch from the ScanForm; the kernels it names live in
 // ccg_dnj_search.h.
 #pragma once
+#include <stdio.h>
 #include <stdlib.h>
 
 #ifdef __HIPCC__
@@ -19,6 +20,7 @@
                          // of this many bands below them (DnjGrid::top/bands)
 #define DNJ_BANDS_MAX 128  // CCG_S_BANDS up to this (two bands per lane of k_dnj_plan's wave 0)
 #define SEG 2048         // cells per rescan unit (TB threads x 8)
+#define LB_SEG_DEFAULT (2 * SEG)   // cells per unit of a run with the block bounds (DnjGrid::seg_lb)
 #define TBF 1024         // threads of k_dnj_plan (one block)
 #define FIND_RPT 16      // rows per thread per step of k_dnj_plan's listing (one step up to n = 15361)
 #define PLAN_MAXB 256    // blocks of k_dnj_plan (one listing step of LT * FR rows each)
@@ -79,6 +81,14 @@ struct DnjGrid {
 	// the bounded scan is latency-bound, and the group form has a quarter of the units at 131 VGPRs
 	// (3 waves/SIMD) against 68 (7): off by default
 	int lb_groups = 0;
+	// the bounded units' length in cells (a multiple of 64, at most 8 SEG).  A bounded unit is a latency chain
+	// (threshold and sum, up to 256 block bounds and column-sum maxima, the surviving cells) whatever its length,
+	// but a long unit leaves a row's surviving blocks to fewer waves.  Measured on the headline tree beside the
+	// dist (tree_s, profiles/step_legs.json): seg(n) of a run without bounds 6.022 s, 2048 throughout 6.385,
+	// 4096 5.921, 8192 6.078, 16384 6.752: LB_SEG_DEFAULT is 4096 (a floor: seg_bounded()).  seg_lb: set by tree_run_t once the bounds
+	// are bound (0: none, seg(n) as without them); seg_lb_knob: CCG_SEG_LB (tests and sweeps; 0: the default,
+	// -1 from CCG_SEG_LB=0: the lengths of a run without bounds)
+	int seg_lb = 0, seg_lb_knob = 0;
 	int scan_vblk = 1;  // with pruning: also the bound from every row above (the requeue's per-block
 	                    // minima of V_k = max(q at the partner cell, Q_k)) (CCG_SCAN_VBLK=0: off)
 	void load() {
@@ -109,6 +119,13 @@ struct DnjGrid {
 		if(const char *e = getenv("CCG_SCAN_LB")) lb = atoi(e);
 		if(const char *e = getenv("CCG_LB_MIN_N")) lb_min_n = atoi(e);
 		if(const char *e = getenv("CCG_LB_GROUPS")) lb_groups = atoi(e);
+		if(const char *e = getenv("CCG_SEG_LB")) {
+			char *end;
+			const long v = strtol(e, &end, 10);
+			if(end != e && !*end && v == 0) seg_lb_knob = -1;
+			else if(end != e && !*end && v >= 64 && v <= 8 * SEG && v % 64 == 0) seg_lb_knob = (int) v;
+			else fprintf(stderr, "ccphylo_amd: CCG_SEG_LB=%s ignored (0, or a multiple of 64 up to %d)\n", e, 8 * SEG);
+		}
 	}
 	// k_dnj_plan's last argument: the Q-load delay (low 14 bits), bits 14-15 the
 	// test knob test_withhold, bit 16 turns
@@ -163,6 +180,10 @@ struct DnjGrid {
 		m = m < 1 ? 1 : m > 8 ? 8 : m;
 		return m * SEG;
 	}
+	// the unit length of a join that scans under the block bounds (ScanForm::seg; seg_lb set): CCG_SEG_LB's as
+	// it is, the default as a floor under seg(n) (from 49152 taxa on that one is longer, so the unit arrays
+	// tree_layout sizes and the plan's UHIST bins hold at every n)
+	int seg_bounded(int n) const { return seg_lb_knob > 0 || seg_lb > seg(n) ? seg_lb : seg(n); }
 	// rows with many units: fold each row's unit partials once (k_dnj_fold)
 	// instead of in every block of k_dnj_join
 	bool prefold(int n) const { return n > prefold_n; }
@@ -220,6 +241,7 @@ struct ScanForm {
 	int sfold;         // ... with this argument (S's entries folded already)
 	unsigned grid;     // the scan's grid
 	int launches;      // launches of the scan leg: the scan, k_dnj_sphase, k_dnj_fold
+	int seg;           // cells per unit of this join's plan, scan, fold and join: seg(n), or seg_bounded(n) under the bounds
 };
 
 // CCG_SCAN_WAVE's value as the form that runs: 0 block; 1-3 wave; 4 16-byte
@@ -234,9 +256,14 @@ inline int dnj_scan_base(int sm) {
 inline ScanForm dnj_scan_form(const DnjGrid &g, int n, int et, bool gen, bool have_lbm) {
 	const int sm = dnj_scan_base(g.scan_mode(n, et));
 	const bool grp = sm == 20 || sm == 21, prefold = g.prefold(n);
-	const bool fits = dnj_umax(n, g.seg(n)) < UHIST;   // the plan's unit histogram covers every row
 	ScanForm f = {};
 	f.tfold = prefold && g.scan_fold && sm >= 1;
+	// the bounded scan is the compacted wave scan (below: f.lb follows from have_lbm && f.cmp; prune 1 needs
+	// FoldTail, so !tfold covers it): where it will run with a length of its own, that length decides `fits`
+	const bool lbseg = have_lbm && g.seg_lb > 0 && !gen && sm >= 4 && g.scan_cmp && !f.tfold &&
+	                   dnj_umax(n, g.seg_bounded(n)) < UHIST;
+	f.seg = lbseg ? g.seg_bounded(n) : g.seg(n);
+	const bool fits = dnj_umax(n, f.seg) < UHIST;   // the plan's unit histogram covers every row
 	// pruning: band mode, no missing entries, a wave form.  1 wants FoldTail;
 	// 2 wants k_dnj_fold, and with row groups the compacted scan (its
 	// enumeration is how the groups skip what k_dnj_sphase pruned)
@@ -284,5 +311,6 @@ inline ScanForm dnj_scan_form_shard(const DnjGrid &g, int n, int et, bool have_l
 	f.lb = have_lbm && sm >= 4;
 	f.grid = g.scan(n);
 	f.launches = 1;
+	f.seg = g.seg(n);
 	return f;
 }

@@ -1040,20 +1040,70 @@ struct XsPre {
 	XsCross cr[XS_PRE_C];
 	XsTie ti;
 };
+// XsPre and the walk's record registers stay registers only while nothing
+// takes a run-time index into them, selects between their addresses or copies
+// a whole record (a block copy with no typed access keeps the record on the
+// stack): every copy goes field by field, and a pick is a select per field
+__device__ __forceinline__ void xs_copy(XsBlk &d, const XsBlk &a) {
+	d.tail = a.tail;
+	d.head = a.head;
+	d.nc = a.nc;
+	d.nt = a.nt;
+	d.tp = a.tp;
+	d.ex0 = a.ex0;
+	d.eh = a.eh;
+	d.bad = a.bad;
+}
+__device__ __forceinline__ void xs_copy(XsCross &d, const XsCross &a) {
+	d.v = a.v;
+	d.run = a.run;
+	d.k = a.k;
+	d.x = a.x;
+	d.R = a.R;
+	d.tb = a.tb;
+}
+__device__ __forceinline__ void xs_copy(XsTie &d, const XsTie &a) {
+	d.k = a.k;
+	d.pi = a.pi;
+	d.R = a.R;
+	d.first = a.first;
+}
+__device__ __forceinline__ void xs_pick(bool c, XsBlk &d, const XsBlk &a) {
+	d.tail = c ? a.tail : d.tail;
+	d.head = c ? a.head : d.head;
+	d.nc = c ? a.nc : d.nc;
+	d.nt = c ? a.nt : d.nt;
+	d.tp = c ? a.tp : d.tp;
+	d.ex0 = c ? a.ex0 : d.ex0;
+	d.eh = c ? a.eh : d.eh;
+	d.bad = c ? a.bad : d.bad;
+}
+__device__ __forceinline__ void xs_pick(bool c, XsCross &d, const XsCross &a) {
+	d.v = c ? a.v : d.v;
+	d.run = c ? a.run : d.run;
+	d.k = c ? a.k : d.k;
+	d.x = c ? a.x : d.x;
+	d.R = c ? a.R : d.R;
+	d.tb = c ? a.tb : d.tb;
+}
 __device__ __forceinline__ void xs_prefetch(const TreeBufs &b, int G, XsPre &p) {
 	const int g = threadIdx.x & 63;
 	if(g < G) {
-		p.blk = b.xblk[g];
+		xs_copy(p.blk, b.xblk[g]);
 #pragma unroll
-		for(int c = 0; c < XS_PRE_C; ++c) p.cr[c] = b.xcr[(size_t) g * XB_CAP + c];
-		p.ti = b.xti[(size_t) g * XB_CAP_T];
+		for(int c = 0; c < XS_PRE_C; ++c) xs_copy(p.cr[c], b.xcr[(size_t) g * XB_CAP + c]);
+		xs_copy(p.ti, b.xti[(size_t) g * XB_CAP_T]);
 	}
 #pragma unroll
 	for(int h = 1; h < XS_PRE_H; ++h)
-		if(g + 64 * h < G) p.bh[h - 1] = b.xblk[g + 64 * h];
+		if(g + 64 * h < G) xs_copy(p.bh[h - 1], b.xblk[g + 64 * h]);
 }
 
-__device__ bool xs_walk_blocks(const TreeBufs &b, int G, double *out, const XsPre *pre, int n, int *why_out) {
+// pre (have_pre): xs_prefetch's registers, picked by selects over constant
+// indices -- a run-time index into them would put the struct on the stack;
+// inlined into its callers for the same reason
+__device__ __forceinline__ bool xs_walk_blocks(const TreeBufs &b, int G, double *out, bool have_pre, const XsPre &pre, int n,
+                                               int *why_out) {
 	(void) n;   // trace stamps only
 	__shared__ XsCross lc[XS_CAP];
 	__shared__ int lcR[XS_CAP], lcT[XS_CAP];   // the crossing's block: Rw, global index of its first tie
@@ -1070,16 +1120,20 @@ __device__ bool xs_walk_blocks(const TreeBufs &b, int G, double *out, const XsPr
 	// every block's summary is in registers (pre, G <= 256): the record loads
 	// of all blocks are issued together below, one round trip (round 5);
 	// otherwise block by block as they come
-	const bool allpre = pre && G <= 64 * XS_PRE_H && b.xs_allpre;
+	const bool allpre = have_pre && G <= 64 * XS_PRE_H && b.xs_allpre;
 	__shared__ int bco[64 * XS_PRE_H], bto[64 * XS_PRE_H], bRw[64 * XS_PRE_H], bex[64 * XS_PRE_H];
 	__shared__ short cown[XS_CAP], town[XS_CAP_T];   // the block of each crossing / tie record
 	for(int g0 = 0; g0 < G; g0 += 64) {
 		const int g = g0 + lane, ph = g0 >> 6;
 		XsBlk s;
 		if(g < G) {
-			s = pre && g0 == 0 ? pre->blk
-			    : allpre       ? pre->bh[ph >= 1 && ph < XS_PRE_H ? ph - 1 : 0]
-			                   : b.xblk[g];
+			if(have_pre && (g0 == 0 || allpre)) {
+				xs_copy(s, pre.blk);
+#pragma unroll
+				for(int q = 0; q < XS_PRE_H - 1; ++q) xs_pick(allpre && ph == q + 1, s, pre.bh[q]);
+			} else {
+				xs_copy(s, b.xblk[g]);
+			}
 		} else {
 			s.tail = 0;
 			s.nc = s.nt = s.tp = s.ex0 = s.bad = 0;
@@ -1101,14 +1155,23 @@ __device__ bool xs_walk_blocks(const TreeBufs &b, int G, double *out, const XsPr
 		} else {
 			for(int c = 0; c < s.nc && c < XB_CAP; ++c) {
 				if(co + c < XS_CAP) {
-					lc[co + c] = pre && g0 == 0 && c < XS_PRE_C ? pre->cr[c < XS_PRE_C ? c : 0] : b.xcr[(size_t) g * XB_CAP + c];
+					if(have_pre && g0 == 0 && c < XS_PRE_C) {
+						XsCross pc;
+						xs_copy(pc, pre.cr[0]);
+#pragma unroll
+						for(int q = 1; q < XS_PRE_C; ++q) xs_pick(c == q, pc, pre.cr[q]);
+						xs_copy(lc[co + c], pc);
+					} else {
+						xs_copy(lc[co + c], b.xcr[(size_t) g * XB_CAP + c]);
+					}
 					lcR[co + c] = Rw;
 					lcT[co + c] = to;
 				}
 			}
 			for(int t = 0; t < s.nt && t < XB_CAP_T; ++t) {
 				if(to + t < XS_CAP_T) {
-					lt[to + t] = pre && g0 == 0 && t == 0 ? pre->ti : b.xti[(size_t) g * XB_CAP_T + t];
+					if(have_pre && g0 == 0 && t == 0) xs_copy(lt[to + t], pre.ti);
+					else xs_copy(lt[to + t], b.xti[(size_t) g * XB_CAP_T + t]);
 					ltR[to + t] = Rw;
 				}
 			}
@@ -1143,7 +1206,7 @@ __device__ bool xs_walk_blocks(const TreeBufs &b, int G, double *out, const XsPr
 			if(q < nx && q < XS_CAP) {
 				const int g = owner(cown, q);
 				cg[m] = g;
-				cv[m] = b.xcr[(size_t) g * XB_CAP + (q - bco[g])];
+				xs_copy(cv[m], b.xcr[(size_t) g * XB_CAP + (q - bco[g])]);
 			}
 		}
 		XsTie tv[XS_CAP_T / 64];
@@ -1155,14 +1218,14 @@ __device__ bool xs_walk_blocks(const TreeBufs &b, int G, double *out, const XsPr
 			if(q < ntot && q < XS_CAP_T) {
 				const int g = owner(town, q);
 				tg[m] = g;
-				tv[m] = b.xti[(size_t) g * XB_CAP_T + (q - bto[g])];
+				xs_copy(tv[m], b.xti[(size_t) g * XB_CAP_T + (q - bto[g])]);
 			}
 		}
 #pragma unroll
 		for(int m = 0; m < 2; ++m) {
 			const int q = lane + 64 * m;
 			if(cg[m] >= 0) {
-				lc[q] = cv[m];
+				xs_copy(lc[q], cv[m]);
 				lcR[q] = bRw[cg[m]];
 				lcT[q] = bto[cg[m]];
 			}
@@ -1171,7 +1234,7 @@ __device__ bool xs_walk_blocks(const TreeBufs &b, int G, double *out, const XsPr
 		for(int m = 0; m < XS_CAP_T / 64; ++m) {
 			const int q = lane + 64 * m;
 			if(tg[m] >= 0) {
-				lt[q] = tv[m];
+				xs_copy(lt[q], tv[m]);
 				ltR[q] = bRw[tg[m]];
 			}
 		}
@@ -1270,8 +1333,8 @@ __device__ bool xs_walk_blocks(const TreeBufs &b, int G, double *out, const XsPr
 // wave 0 of a consumer (k_dnj_requeue / k_nj_pop / k_hnj_update): the new
 // row sum of j and its count.  *chain: the whole block must run the serial
 // chain over b.contrib (rare: a failed check of the parallel form).
-__device__ void row_sum_j_wave(const TreeBufs &b, int n, bool exact, bool general, double *sd, int *nj, bool *need,
-                               bool *chain) {
+__device__ __forceinline__ void row_sum_j_wave(const TreeBufs &b, int n, bool exact, bool general, double *sd, int *nj,
+                                               bool *need, bool *chain) {
 	const int G = (int) cdiv(n, TB);
 	XsPre pre;
 	if(exact) xs_prefetch(b, G, pre);
@@ -1282,7 +1345,7 @@ __device__ void row_sum_j_wave(const TreeBufs &b, int n, bool exact, bool genera
 	if(*need) {
 		double r;
 		int why = 0;
-		if(xs_walk_blocks(b, G, &r, exact ? &pre : nullptr, n, &why)) {
+		if(xs_walk_blocks(b, G, &r, exact, pre, n, &why)) {
 			*sd = r;
 		} else {
 			*chain = true;

@@ -696,8 +696,8 @@ __global__ __launch_bounds__(256, 1) void k_snp_mfma2(const uint2 *__restrict__ 
 // through CCPHYLO_AMD_ENGINE): k_snp_mfma3 stamps s_memtime around the parts
 // of each chunk of its main loop and sums the differences per part; lane 0 of
 // waves 0 and 3 store the sums to a buffer of their own, [item][wave][8]:
-// steps 0, 1, 2, step 3 up to the counted wait, the wait and the barrier, from
-// the barrier to the last DMA issue, the rest of step 3, the chunks summed.
+// steps 0, 1, 2, step 3 up to the counted wait, the wait and the barrier,
+// component 1 of step 3, the rest of step 3, the chunks summed.
 // The stamps fence the schedule (sched_barrier) and drain the LDS reads in
 // flight, so the shares are the record, not the run time.  The normal build
 // holds no stamp.
@@ -820,7 +820,6 @@ __global__ __launch_bounds__(256, 1) void k_snp_mfma3(const uint2 *__restrict__ 
 	                                                              0, MFMA_SCALE1)
 	for(int c = 0; c < NST3 - 1 && c < nch; ++c) issue(c);
 	land(0);
-	if(NST3 - 1 < nch) issue(NST3 - 1);
 	uint2 a[4], b[4];
 	v8i_t f0[4], g0[4];
 	rd(0, a, b);
@@ -836,9 +835,10 @@ __global__ __launch_bounds__(256, 1) void k_snp_mfma3(const uint2 *__restrict__ 
 	// the matrix pipe does not idle while a wave spreads (k_snp_mfma2: 16 MFMAs,
 	// then the spreads; ~60% MFMA busy, profiles/r06_dist_clock.json):
 	//   comp 0 (f0, g0) + the spreads of lo (f1, g1)
-	//   comp 1 (f1, g1) + the xors (x0, y0), the next step's LDS reads, and in a
-	//                     chunk's last step the 8 DMA pieces of chunk c + NST3
+	//   comp 1 (f1, g1) + the xors (x0, y0), the next step's LDS reads
 	//   comp 2 (x0, y0) + the next step's spreads of hi (f0, g0)
+	// and two of the 8 DMA pieces of chunk c + NST3 - 1 in each of chunk c's four
+	// steps (PC3 / PK3 below)
 	// The order is written out gap by gap and fenced: one MFMA, half a spread
 	// (4 or 3 VALU) or half an xor (2 VALU), then sched_barrier(0), so no gap
 	// holds more than 4 VALU (5 with a piece's address add) and the compiler
@@ -847,15 +847,35 @@ __global__ __launch_bounds__(256, 1) void k_snp_mfma3(const uint2 *__restrict__ 
 	// (ORD: f[0], g[0..3], f[1..3]), each at least 3 MFMAs before its reader.
 	// A chunk's last step waits for the next chunk (counted vmcnt + barrier)
 	// between comp 0 and comp 1, fenced on both sides, so that step's reads
-	// follow the barrier and every other MFMA-free instruction of the chunk
-	// open (the pieces and their M0 and address work) sits in a gap of comp 1.
+	// follow the barrier.
+	// The ring's pieces.  Chunk x lives in stage x % NST3.  Iteration c of the
+	// steady loop issues the pieces of chunk c + NST3 - 1 into the stage of
+	// chunk c - 1: free, because every wave passed the barrier in chunk c - 1's
+	// last step, and each had consumed its last LDS reads of that chunk (the
+	// .y words of step 4 c - 1, spread in that step's comp 0) before it arrived
+	// there.  Two pieces per step, in gaps that carry no LDS read, never in
+	// adjacent gaps, so that the four waves' 1-KiB pieces do not queue behind
+	// each other (all 8 in one component ran at the CU's LDS-DMA rate, ~120
+	// cycles a piece).  Step 3's two go before the counted wait: at that wait
+	// chunks c + 1, c + 2 and c + 3 are outstanding, 24 pieces issued in that
+	// order, so vmcnt(16) is exactly "chunk c + 1 landed".  The prologue issues
+	// chunks 0 .. NST3 - 2 only.  The steady loop ends with c = nch - NST3 + 1:
+	// the second copy starts with chunks c + 1 .. nch - 1 outstanding, which is
+	// what land()'s run-time count assumes.
 #define GAP3() __builtin_amdgcn_sched_barrier(0)
+	// PC3(s, i) / PK3(s, i): the component and the gap of piece 2 s + i in step s of a chunk: component 1's
+	// gaps 5 and 11 (its gaps 0 and 1 carry the LDS reads); in step 3 component 0's, before the wait
+#define PC3(S, I) ((S) == 3 ? 0 : 1)
+#define PK3(S, I) ((I) ? 11 : 5)
 	// OPEN: 0 = no chunk opens here; 1 = the next chunk opens, nothing left to
-	// issue (the last NST3 - 1 opens of a tile); 2 = it opens, chunk cn + NST3 - 1
-	// exists and 2 chunks stay in flight (vmcnt(16), known at compile time)
-	auto step = [&](auto OPEN, auto MORE, int gs) {
+	// issue (the last NST3 - 2 opens of a tile); 2 = it opens in the steady loop:
+	// 2 chunks stay in flight (vmcnt(16), known at compile time).
+	// ISS: -1, or this step's index in its chunk: it issues pieces 2 ISS, 2 ISS + 1
+	auto step = [&](auto OPEN, auto MORE, auto ISS, int gs) {
 		constexpr int open = decltype(OPEN)::value;
 		constexpr bool more = decltype(MORE)::value;
+		constexpr int iss = decltype(ISS)::value;
+		const int ci = (gs >> 2) + NST3 - 1;   // iss >= 0: the chunk whose pieces 2 iss, 2 iss + 1 this step issues
 		v8i_t f1[4], g1[4], x0[4], y0[4];
 #pragma unroll
 		for(int k = 0; k < 16; ++k) {
@@ -863,6 +883,8 @@ __global__ __launch_bounds__(256, 1) void k_snp_mfma3(const uint2 *__restrict__ 
 			const int j = k >> 1;   // operand j of ORD
 			if(j == 0 || j > 4) fp4_spread_half(f1[j ? j - 4 : 0], a[j ? j - 4 : 0].y, k & 1);
 			else fp4_spread_half(g1[j - 1], b[j - 1].y, k & 1);
+			if(iss >= 0 && PC3(iss, 0) == 0 && k == PK3(iss, 0)) issue1(ci, 2 * iss);
+			if(iss >= 0 && PC3(iss, 1) == 0 && k == PK3(iss, 1)) issue1(ci, 2 * iss + 1);
 			GAP3();
 		}
 		const int cn = (gs + 1) >> 2;   // open: the next step opens chunk cn
@@ -889,7 +911,8 @@ __global__ __launch_bounds__(256, 1) void k_snp_mfma3(const uint2 *__restrict__ 
 			else fp4_xor_spread_half(y0[j - 1], g0[j - 1], g1[j - 1], k & 1);
 			if(more && k == 0) rd1(gs + 1, 0, an);   // the next step's LDS reads, behind the barrier: A, then B
 			if(more && k == 1) rd1(gs + 1, 1, bn);
-			if(open == 2 && (k & 1)) issue1(cn + NST3 - 1, k >> 1);   // one piece in every other gap
+			if(iss >= 0 && PC3(iss, 0) == 1 && k == PK3(iss, 0)) issue1(ci, 2 * iss);
+			if(iss >= 0 && PC3(iss, 1) == 1 && k == PK3(iss, 1)) issue1(ci, 2 * iss + 1);
 			GAP3();
 		}
 		if(open == 2) ST3(5);
@@ -901,6 +924,8 @@ __global__ __launch_bounds__(256, 1) void k_snp_mfma3(const uint2 *__restrict__ 
 				if(j == 0 || j > 4) fp4_spread_half(f0[j ? j - 4 : 0], an[j ? j - 4 : 0].x, k & 1);
 				else fp4_spread_half(g0[j - 1], bn[j - 1].x, k & 1);
 			}
+			if(iss >= 0 && PC3(iss, 0) == 2 && k == PK3(iss, 0)) issue1(ci, 2 * iss);
+			if(iss >= 0 && PC3(iss, 1) == 2 && k == PK3(iss, 1)) issue1(ci, 2 * iss + 1);
 			GAP3();
 		}
 		if(more) {
@@ -914,28 +939,29 @@ __global__ __launch_bounds__(256, 1) void k_snp_mfma3(const uint2 *__restrict__ 
 	typedef std::integral_constant<int, 0> O0;
 	typedef std::integral_constant<int, 1> O1;
 	typedef std::integral_constant<int, 2> O2;
+	typedef std::integral_constant<int, -1> NI;
 	typedef std::true_type MT;
 	ST3(-1);
 	int c = 0;
-	for(; c + NST3 < nch; ++c) {   // 4 steps, the last one opens chunk c + 1 and issues chunk c + NST3
-		step(O0(), MT(), 4 * c + 0);
+	for(; c + NST3 - 1 < nch; ++c) {   // 4 steps, each issues 2 pieces of chunk c + NST3 - 1; the last one opens chunk c + 1
+		step(O0(), MT(), std::integral_constant<int, 0>(), 4 * c + 0);
 		ST3(0);
-		step(O0(), MT(), 4 * c + 1);
+		step(O0(), MT(), std::integral_constant<int, 1>(), 4 * c + 1);
 		ST3(1);
-		step(O0(), MT(), 4 * c + 2);
+		step(O0(), MT(), std::integral_constant<int, 2>(), 4 * c + 2);
 		ST3(2);
-		step(O2(), MT(), 4 * c + 3);
+		step(O2(), MT(), std::integral_constant<int, 3>(), 4 * c + 3);
 		ST3(6);
 	}
 	for(; c + 1 < nch; ++c) {   // the chunks with nothing left to issue, but the last
-		step(O0(), MT(), 4 * c + 0);
-		step(O0(), MT(), 4 * c + 1);
-		step(O0(), MT(), 4 * c + 2);
-		step(O1(), MT(), 4 * c + 3);
+		step(O0(), MT(), NI(), 4 * c + 0);
+		step(O0(), MT(), NI(), 4 * c + 1);
+		step(O0(), MT(), NI(), 4 * c + 2);
+		step(O1(), MT(), NI(), 4 * c + 3);
 	}
 #ifdef CCG_DIST_STAMPS
 	if(ccg_dist_stamp_buf && lane == 0 && (wid == 0 || wid == 3)) {
-		stamp_sum[7] = nch > NST3 ? nch - NST3 : 0;
+		stamp_sum[7] = nch > NST3 - 1 ? nch - (NST3 - 1) : 0;
 		unsigned long long *sb =
 		    ccg_dist_stamp_buf + ((t0 - ccg_dist_stamp_item0 + blockIdx.x) * 2 + (wid ? 1 : 0)) * ST3_SLOTS;
 		for(int k = 0; k < ST3_SLOTS; ++k) sb[k] = stamp_sum[k];
@@ -943,13 +969,15 @@ __global__ __launch_bounds__(256, 1) void k_snp_mfma3(const uint2 *__restrict__ 
 #endif
 	{   // the last chunk
 		const int g = 4 * (nch - 1);
-		step(O0(), MT(), g + 0);
-		step(O0(), MT(), g + 1);
-		step(O0(), MT(), g + 2);
-		step(O0(), std::false_type(), g + 3);
+		step(O0(), MT(), NI(), g + 0);
+		step(O0(), MT(), NI(), g + 1);
+		step(O0(), MT(), NI(), g + 2);
+		step(O0(), std::false_type(), NI(), g + 3);
 	}
 #undef MF3
 #undef GAP3
+#undef PC3
+#undef PK3
 	// epilogue: k_snp_mfma2's
 	const int L3 = 3 * 32 * Wl;
 #pragma unroll

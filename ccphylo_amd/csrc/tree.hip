@@ -1639,6 +1639,10 @@ static size_t tree_layout(TreeBufs *bp, int n, char *m) {
 		const int k = 16384 * mm - 1;
 		if(k <= n && dnj_umax(k, g.seg(k)) > umax) umax = dnj_umax(k, g.seg(k));
 	}
+	// (a run with the block bounds never cuts shorter units than these by default, DnjGrid::seg_bounded.
+	// CCG_SEG_LB, a knob for tests and sweeps, may: where the bounds can bind, room for its units too -- 64
+	// cells at 50k taxa are 782 units per candidate row, 470 MB)
+	if(g.seg_lb_knob > 0 && g.lb && n > g.lb_min_n && dnj_umax(n, g.seg_lb_knob) > umax) umax = dnj_umax(n, g.seg_lb_knob);
 	size_t cunits = ncand * (size_t) umax;
 	if(cunits < JOIN_UPRE) cunits = JOIN_UPRE;
 	const size_t nq = (size_t) nj_blocks(n) + 1;
@@ -1791,7 +1795,7 @@ static int tree_alloc_ctx(ccg_ctx *c, TreeWork *w, int n) {
 template <int ET, bool GEN>
 static void enqueue_plan(hipStream_t st, typename Elem<ET>::T *D, double bs, const TreeBufs &b, int n, int first,
                          const ScanForm &f) {
-	const int seg = g_grid.seg(n);
+	const int seg = f.seg;
 	const unsigned gp = g_grid.plan_blocks(n);
 	if(g_grid.bands(n)) k_dnj_plan<ET, GEN, DenseRows, true><<<gp + f.helpers, TBF, 0, st>>>(D, bs, b, n, first, DenseRows(), seg, g_grid.top(n), g_grid.bands(n), g_grid.plan_flags(f.prune != 0, f.helpers));
 	else k_dnj_plan<ET, GEN, DenseRows, false><<<gp, TBF, 0, st>>>(D, bs, b, n, first, DenseRows(), seg, g_grid.top(n), 0, g_grid.plan_flags());
@@ -1851,8 +1855,9 @@ static int enqueue_iteration(hipStream_t st, typename Elem<ET>::T *D, double bs,
 	const unsigned gn = cdiv(n, TB);
 	const int general = GEN;
 	if(method == CCG_TREE_DNJ) {
-		const int seg = g_grid.seg(n), prefold = g_grid.prefold(n);
+		const int prefold = g_grid.prefold(n);
 		const ScanForm f = dnj_scan_form(g_grid, n, ET, GEN, b.lbm != NULL);
+		const int seg = f.seg;
 		// one-phase search: k_dnj_plan lists S and the rows below it under the
 		// partner-cell bound, the scan rescans them all (with pruning: S first,
 		// by k_dnj_sphase or the plan's helpers, the rest under S's bound table)
@@ -2090,8 +2095,20 @@ static int tree_run_t(ccg_ctx *ctx, const ccg_tree_args *a, void *Dd, ccg_join *
 			// S-bound pruning no longer pays beside the bounded scan (headline tree, profiled: 4.61 s
 			// without, 4.78 s with the plan's helpers and the compaction); CCG_SCAN_PRUNE still forces it
 			if(!getenv("CCG_SCAN_PRUNE")) g_grid.scan_prune = 0;
-			// the bounded units are short: twice the waves (headline tree 4.84 -> 4.74 s, profiled)
-			if(!cmp_env) g_grid.cmp_blocks = cmp_share(2048);
+			g_grid.seg_lb = g_grid.seg_lb_knob < 0 ? 0 : g_grid.seg_lb_knob ? g_grid.seg_lb_knob : LB_SEG_DEFAULT;
+			// the dense enumeration deals the units round-robin over a grid that must be resident at once (a
+			// block that starts when another ends doubles the span): as many blocks as the bounded scan's
+			// registers let the context's CUs hold
+			if(!cmp_env) {
+				const ScanForm f = dnj_scan_form(g_grid, n0, ET, false, true);
+				int per_cu = 0;
+				const void *fn = f.prune == 2 ? (const void *) k_dnj_scan_v<ET, DenseRows, NoTail, false, 2, true, true>
+				                              : (const void *) k_dnj_scan_v<ET, DenseRows, NoTail, false, 0, true, true>;
+				if(f.kernel == SCAN_GROUP_CMP) fn = (const void *) k_dnj_scan_gc<ET, 4, 8, false, true>;
+				CCG_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, TB, 0));
+				const int cus = ctx->cus > 0 && ctx->cus < ctx->ncu ? ctx->cus : ctx->ncu;
+				g_grid.cmp_blocks = per_cu * cus > 64 ? per_cu * cus : 64;
+			}
 		} else {
 			(void) hipGetLastError();   // no room: the run goes without (the same joins)
 		}

@@ -13,7 +13,7 @@ import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-PARTS = ["step 0", "step 1", "step 2", "step 3 up to the wait", "wait + barrier", "barrier to last DMA issue",
+PARTS = ["step 0", "step 1", "step 2", "step 3 up to the wait", "wait + barrier", "component 1 of step 3",
          "rest of step 3"]
 
 
