@@ -9,6 +9,15 @@
  * np count-matrix metrics, the tree methods upgma and frank) are
  * refused with an error instead of being silently approximated.
  *
+ * Every command is: a struct of its options with the defaults in its
+ * initialiser, a table of option rows in help order, a cli_cmd descriptor, one
+ * cli_parse (host/cliopt.c walks argv and prints `-h` from the same table),
+ * the post-parse checks, the run.  What differs between commands' argument
+ * handling -- message formats that mirror the reference's cmdline.c or the
+ * command's own main_*, a bare `--`, one input or a list -- is descriptor data;
+ * an oddity of one option (`merge -H` ends its short-option word) is a bit on
+ * its row.
+ *
  * Extra (not in the reference): `tree --fast_sums` uses a fixed-order
  * parallel row sum instead of the reference's serial one;
  * `--device N` selects the GPU; `tree --gpus G [--transport rccl|host]`
@@ -32,51 +41,52 @@
 #include "ccphylo_amd.h"
 #include "ccphylo_host.h"
 #include "mgpu.h"
+#include "cliopt.h"
+
+/* the descriptors' message formats: cmdline.c's, and tsv2phy.c's and merge.c's own */
+#define UNKNOWN_CMDLINE "Unknown argument:\t\"%s\"\n"
+#define UNKNOWN_OWN "Unknown argument or option: \"%s\"\n"
+#define EXTRA_CMDLINE "Unexpected non-option argument(s).\n"
+#define EXTRA_OWN "Too many non-option arguments handed.\n"
 
 static void die_opt(const char *kind, const char *opt) {
 	fprintf(stderr, "%s argument:\t\"%s\"\n", kind, opt);
 	exit(1);
 }
 
-static int is_num(const char *s) {
-	char *e;
-	if(!s || !*s) return 0;
-	strtod(s, &e);
-	return *e == 0;
+/* "-" is stdout */
+static FILE *open_out(const char *name) {
+	return (name[0] == '-' && name[1] == 0) ? stdout : fopen(name, "wb");
 }
 
-typedef struct {
-	int argc, k;
-	char **argv;
-} Args;
-
-/* value of an option: attached ("-x5", "--opt=5") or the next argv word */
-static char *opt_value(Args *A, const char *attached, const char *opt) {
-	if(attached && *attached) return (char *) attached;
-	if(A->k + 1 < A->argc) return A->argv[++A->k];
-	die_opt("Missing", opt);
-	return NULL;
+/* dist.c:74-84: the -n file; one stream where it names the -o file */
+static FILE *open_nout(const char *noutname, const char *outname, FILE *out) {
+	return strcmp(noutname, outname) ? open_out(noutname) : out;
 }
 
-/* optional numeric value (cmdline.c getdDefArg): only if it does not start with '-' */
-static double opt_dvalue_def(Args *A, const char *attached, double def, const char *opt) {
-	const char *v = NULL;
-	if(attached && *attached) {
-		v = attached;
-	} else if(A->k + 1 < A->argc && A->argv[A->k + 1][0] != '-') {
-		v = A->argv[++A->k];
+/* the message of a failed open; the status is errno where the caller passes it on, else 1 */
+static int errno_fail(int pass) {
+	fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
+	return (pass && errno) ? errno : 1;
+}
+
+/* the tree methods of this command line: `tree -m`, --tree_method of the fused pipelines, the -M listing */
+static const struct {
+	const char *name;
+	int id;
+	const char *text;
+} tree_methods[] = {{"nj", CCG_TREE_NJ, "Neighbor-Joining"},     {"cf", CCG_TREE_CF, "K-means Closest First"},
+                    {"ff", CCG_TREE_FF, "K-means Furthest First"}, {"mn", CCG_TREE_MN, "Minimum Neighbors"},
+                    {"hnj", CCG_TREE_HNJ, "Heuristic Neighbor-Joining"}, {"dnj", CCG_TREE_DNJ, "Dynamic Neighbor-Joining"}};
+
+static int tree_method_id(const char *name) {
+	for(size_t k = 0; k < sizeof(tree_methods) / sizeof(tree_methods[0]); ++k) {
+		if(!strcmp(name, tree_methods[k].name)) return tree_methods[k].id;
 	}
-	if(!v) return def;
-	if(!is_num(v)) die_opt("Invalid", opt);
-	return strtod(v, NULL);
+	return -1;
 }
 
-static long opt_num(Args *A, const char *attached, const char *opt) {
-	char *v = opt_value(A, attached, opt), *e;
-	long x = strtol(v, &e, 10);
-	if(*e) die_opt("Invalid", opt);
-	return x;
-}
+static const cli_name transports[] = {{"rccl", CCQ_TRANSPORT_RCCL}, {"host", CCQ_TRANSPORT_HOST}, {NULL, 0}};
 
 static ccg_ctx *open_gpu(int device) {
 	ccg_ctx *ctx = NULL;
@@ -89,42 +99,43 @@ static ccg_ctx *open_gpu(int device) {
 }
 
 /* ================================================================ tree */
-static int tree_help(FILE *out) {
-	fprintf(out, "#CCPhylo forms tree(s) in newick format given a set of phylip distance matrices.\n");
-	fprintf(out, "#   %-24s\t%-32s\t%s\n", "Options are:", "Desc:", "Default:");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'i', "input", "Input file", "stdin");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'o', "output", "Output file", "stdout");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'S', "separator", "Separator", "\\t");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'q', "quotes", "Quote taxa", "\\0");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'x', "print_precision", "Floating point print precision", "9");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'm', "method", "Tree construction method.", "dnj");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'M', "method_help", "Help on option \"-m\"", "");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'f', "flag", "Output flags", "0");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'F', "flag_help", "Help on option \"-f\"", "");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'p', "float_precision", "Float precision on distance matrix", "False / double");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 's', "short_precision", "Short precision on distance matrix", "False / double / 1e0");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'b', "byte_precision", "Byte precision on distance matrix", "False / double / 1e0");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'g', "free", "Gradually free up D", "False");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'H', "mmap", "Allocate matrix on the disk", "False");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'T', "tmp", "Set directory for temporary files", "");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 't', "threads", "Number of threads", "1");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'h', "help", "Shows this helpmessage", "");
-	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "gpus", "Shard the matrix over G GPUs (nj, dnj)", "off");
-	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "transport", "rccl / host collectives for --gpus", "rccl");
-	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "fast_sums", "Parallel row sums (not the reference's)", "False");
-	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "phycmp", "Compare each tree's path lengths with its matrix", "off");
-	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "phycmp_flag", "phycmp -f flags for --phycmp", "1");
-	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "device", "First GPU", "0");
-	return out == stderr;
-}
+typedef struct {
+	const char *in, *outname, *method, *cmpname;
+	int cmpflag, flag, precision, fast, device, stats, gpus, transport;
+	cli_prec pr;   /* etype, byte scale */
+	char sep, quotes;
+} TreeOpts;
 
-/* --transport value */
-static int transport_id(const char *v) {
-	if(!strcmp(v, "rccl")) return CCQ_TRANSPORT_RCCL;
-	if(!strcmp(v, "host")) return CCQ_TRANSPORT_HOST;
-	die_opt("Invalid", "\"--transport\"");
-	return -1;
-}
+#define F(f) offsetof(TreeOpts, f)
+static const cli_opt tree_opts[] = {
+	{'i', "input", CLI_STR, F(in), 0, "Input file", "stdin"},
+	{'o', "output", CLI_STR, F(outname), 0, "Output file", "stdout"},
+	{'S', "separator", CLI_CHAR, F(sep), 0, "Separator", "\\t"},
+	{'q', "quotes", CLI_CHAR, F(quotes), 0, "Quote taxa", "\\0"},
+	{'x', "print_precision", CLI_INT, F(precision), 0, "Floating point print precision", "9"},
+	{'m', "method", CLI_STR, F(method), 0, "Tree construction method.", "dnj"},
+	{'M', "method_help", CLI_UNSET, F(method), 0, "Help on option \"-m\"", ""},
+	{'f', "flag", CLI_INT, F(flag), 0, "Output flags", "0"},
+	{'F', "flag_help", CLI_FLAG, F(flag), -1, "Help on option \"-f\"", ""},
+	{'p', "float_precision", CLI_FLAG, F(pr.mark), 4, "Float precision on distance matrix", "False / double"},
+	{'s', "short_precision", CLI_PREC, F(pr), 2, "Short precision on distance matrix", "False / double / 1e0"},
+	{'b', "byte_precision", CLI_PREC, F(pr), 1, "Byte precision on distance matrix", "False / double / 1e0"},
+	{'g', "free", CLI_IGNORE, 0, 0, "Gradually free up D", "False"},   /* host memory knobs: no effect on HBM */
+	{'H', "mmap", CLI_IGNORE, 0, 0, "Allocate matrix on the disk", "False"},
+	{'T', "tmp", CLI_DROP, 0, 0, "Set directory for temporary files", ""},
+	{'t', "threads", CLI_DROP, 0, 1, "Number of threads", "1"},
+	{'h', "help", CLI_HELP, 0, 0, "Shows this helpmessage", ""},
+	{0, "gpus", CLI_INT, F(gpus), 0, "Shard the matrix over G GPUs (nj, dnj)", "off"},
+	{0, "transport", CLI_ENUM, F(transport), 0, "rccl / host collectives for --gpus", "rccl", 0, transports},
+	{0, "fast_sums", CLI_FLAG, F(fast), 1, "Parallel row sums (not the reference's)", "False"},
+	{0, "phycmp", CLI_STR, F(cmpname), 0, "Compare each tree's path lengths with its matrix", "off"},
+	{0, "phycmp_flag", CLI_INT, F(cmpflag), 0, "phycmp -f flags for --phycmp", "1"},
+	{0, "device", CLI_INT, F(device), 0, "First GPU", "0"},
+	{0, "stats", CLI_FLAG, F(stats), 1},
+	{0}};
+static const cli_cmd tree_cmd = {"#CCPhylo forms tree(s) in newick format given a set of phylip distance matrices.",
+                                 tree_opts, UNKNOWN_CMDLINE, EXTRA_CMDLINE, 1, 0, F(in)};
+#undef F
 
 static int perm_by_name(char **names1, char **names2, int n, int32_t *perm, char *msg, size_t msglen);
 
@@ -133,8 +144,9 @@ static int perm_by_name(char **names1, char **names2, int n, int32_t *perm, char
  * replayed into W_dev (n(n-1)/2 cells, free by now), the rows are mapped onto
  * the matrix's by name, and A_dev -- the matrix as loaded -- is compared with
  * it as `phycmp --by_name matrix tree-matrix` does.  0, or 1 with a message. */
-static int tree_phycmp(ccg_ctx *ctx, FILE *cmp, int cmpflag, const char *nwck, char **taxa, int n, int et,
+static int tree_phycmp(ccg_ctx *ctx, const TreeOpts *o, FILE *cmp, const char *nwck, char **taxa, int n,
                        const void *A_dev, void *W_dev) {
+	const int et = o->pr.mark;
 	char **leaves = NULL;
 	ccq_split *splits = NULL;
 	int nl = 0, rc;
@@ -165,7 +177,7 @@ static int tree_phycmp(ccg_ctx *ctx, FILE *cmp, int cmpflag, const char *nwck, c
 			fprintf(stderr, "ccphylo_amd: tree --phycmp failed: %s\n", ccg_strerror(rc));
 			bad = 1;
 		} else {
-			ccq_print_phycmp(cmp, &sums, (int64_t) n * (n - 1) / 2, cmpflag);
+			ccq_print_phycmp(cmp, &sums, (int64_t) n * (n - 1) / 2, o->cmpflag);
 			fflush(cmp);
 		}
 	}
@@ -176,85 +188,11 @@ static int tree_phycmp(ccg_ctx *ctx, FILE *cmp, int cmpflag, const char *nwck, c
 }
 
 static int main_tree(int argc, char **argv) {
-	const char *in = "-", *outname = "-", *method = "dnj", *cmpname = NULL;
-	int cmpflag = 1;
-	int flag = 0, precision = 9, et = 8, fast = 0, device = 0, stats = 0, gpus = 0, transport = CCQ_TRANSPORT_RCCL;
-	char sep = '\t', quotes = 0;
-	double bs = 1.0;
-	Args A = {argc, 0, argv};
-	for(A.k = 1; A.k < argc; ++A.k) {
-		char *a = argv[A.k];
-		if(a[0] != '-' || a[1] == 0) {
-			in = a;
-			if(A.k + 1 < argc) {
-				fprintf(stderr, "Unexpected non-option argument(s).\n");
-				return 1;
-			}
-			break;
-		}
-		if(a[1] == '-') {
-			char *name = a + 2, *eq = strchr(name, '=');
-			char *att = NULL;
-			if(eq) {
-				*eq = 0;
-				att = eq + 1;
-			}
-			if(*name == 0) { continue; }
-			else if(!strcmp(name, "input")) in = opt_value(&A, att, "input");
-			else if(!strcmp(name, "output")) outname = opt_value(&A, att, "output");
-			else if(!strcmp(name, "separator")) sep = opt_value(&A, att, "separator")[0];
-			else if(!strcmp(name, "quotes")) quotes = opt_value(&A, att, "quotes")[0];
-			else if(!strcmp(name, "print_precision")) precision = (int) opt_num(&A, att, "print_precision");
-			else if(!strcmp(name, "method")) method = opt_value(&A, att, "method");
-			else if(!strcmp(name, "method_help")) method = "mh";
-			else if(!strcmp(name, "flag")) flag = (int) opt_num(&A, att, "flag");
-			else if(!strcmp(name, "flag_help")) flag = -1;
-			else if(!strcmp(name, "threads")) (void) opt_num(&A, att, "threads");
-			else if(!strcmp(name, "float_precision")) et = 4;
-			else if(!strcmp(name, "short_precision")) { et = 2; bs = opt_dvalue_def(&A, att, bs, "short_precision"); }
-			else if(!strcmp(name, "byte_precision")) { et = 1; bs = opt_dvalue_def(&A, att, bs, "byte_precision"); }
-			else if(!strcmp(name, "free") || !strcmp(name, "mmap")) { /* host memory knobs: no effect on HBM */ }
-			else if(!strcmp(name, "tmp")) (void) opt_value(&A, att, "tmp");
-			else if(!strcmp(name, "fast_sums")) fast = 1;
-			else if(!strcmp(name, "device")) device = (int) opt_num(&A, att, "device");
-			else if(!strcmp(name, "gpus")) gpus = (int) opt_num(&A, att, "gpus");
-			else if(!strcmp(name, "transport")) transport = transport_id(opt_value(&A, att, "transport"));
-			else if(!strcmp(name, "stats")) stats = 1;
-			else if(!strcmp(name, "phycmp")) cmpname = opt_value(&A, att, "phycmp");
-			else if(!strcmp(name, "phycmp_flag")) cmpflag = (int) opt_num(&A, att, "phycmp_flag");
-			else if(!strcmp(name, "help")) return tree_help(stdout);
-			else die_opt("Unknown", a);
-			continue;
-		}
-		for(char *p = a + 1; *p; ++p) {
-			char o = *p, *att = p + 1;
-			int took = 1;
-			switch(o) {
-				case 'i': in = opt_value(&A, att, "i"); break;
-				case 'o': outname = opt_value(&A, att, "o"); break;
-				case 'S': sep = opt_value(&A, att, "S")[0]; break;
-				case 'q': quotes = opt_value(&A, att, "q")[0]; break;
-				case 'x': precision = (int) opt_num(&A, att, "x"); break;
-				case 'm': method = opt_value(&A, att, "m"); break;
-				case 'f': flag = (int) opt_num(&A, att, "f"); break;
-				case 't': (void) opt_num(&A, att, "t"); break;
-				case 'T': (void) opt_value(&A, att, "T"); break;
-				case 's': et = 2; bs = opt_dvalue_def(&A, att, bs, "s"); break;
-				case 'b': et = 1; bs = opt_dvalue_def(&A, att, bs, "b"); break;
-				case 'M': method = "mh"; took = 0; break;
-				case 'F': flag = -1; took = 0; break;
-				case 'p': et = 4; took = 0; break;
-				case 'g': case 'H': took = 0; break;
-				case 'h': return tree_help(stdout);
-				default: {
-					char bad[3] = {'-', o, 0};
-					die_opt("Unknown", bad);
-				}
-			}
-			if(took) break;
-		}
-	}
-	if(flag == -1) {
+	TreeOpts o = {.in = "-", .outname = "-", .method = "dnj", .cmpflag = 1, .precision = 9,
+	              .transport = CCQ_TRANSPORT_RCCL, .pr = {8, 1.0}, .sep = '\t'};
+	int rc = cli_parse(&tree_cmd, argc, argv, &o);
+	if(rc != CLI_GO) return rc;
+	if(o.flag == -1) {
 		fprintf(stdout, "# Format flags output, add them to combine them.\n");
 		fprintf(stdout, "#\n");
 		fprintf(stdout, "#   1:\tStrictly bifurcate the root\n");
@@ -262,63 +200,40 @@ static int main_tree(int argc, char **argv) {
 		fprintf(stdout, "#\n");
 		return 0;
 	}
-	int m;
-	if(!strcmp(method, "dnj")) {
-		m = CCG_TREE_DNJ;
-	} else if(!strcmp(method, "nj")) {
-		m = CCG_TREE_NJ;
-	} else if(!strcmp(method, "hnj")) {
-		m = CCG_TREE_HNJ;
-	} else if(!strcmp(method, "cf")) {
-		m = CCG_TREE_CF;
-	} else if(!strcmp(method, "ff")) {
-		m = CCG_TREE_FF;
-	} else if(!strcmp(method, "mn")) {
-		m = CCG_TREE_MN;
-	} else if(!strcmp(method, "mh")) {
+	if(!o.method || !strcmp(o.method, "mh")) {
 		fprintf(stdout, "# Tree construction methods:\n#\n");
-		fprintf(stdout, "# %-8s\t%s\n", "nj", "Neighbor-Joining");
-		fprintf(stdout, "# %-8s\t%s\n", "cf", "K-means Closest First");
-		fprintf(stdout, "# %-8s\t%s\n", "ff", "K-means Furthest First");
-		fprintf(stdout, "# %-8s\t%s\n", "mn", "Minimum Neighbors");
-		fprintf(stdout, "# %-8s\t%s\n", "hnj", "Heuristic Neighbor-Joining");
-		fprintf(stdout, "# %-8s\t%s\n", "dnj", "Dynamic Neighbor-Joining");
+		for(size_t k = 0; k < sizeof(tree_methods) / sizeof(tree_methods[0]); ++k) {
+			fprintf(stdout, "# %-8s\t%s\n", tree_methods[k].name, tree_methods[k].text);
+		}
 		fprintf(stdout, "#\n");
 		return 0;
-	} else if(!strcmp(method, "upgma") || !strcmp(method, "frank")) {
+	}
+	const int m = tree_method_id(o.method);
+	if(m < 0 && (!strcmp(o.method, "upgma") || !strcmp(o.method, "frank"))) {
 		/* upgma: the engine has it (CCG_TREE_UPGMA, C ABI and Python); this command line does not offer it yet */
-		fprintf(stderr, "ccphylo_amd: tree method \"%s\" is not implemented by this command line (nj, cf, ff, mn, hnj, dnj are).\n", method);
-		return 1;
-	} else {
-		die_opt("Invalid", "\"-m\"");
+		fprintf(stderr, "ccphylo_amd: tree method \"%s\" is not implemented by this command line (nj, cf, ff, mn, hnj, dnj are).\n", o.method);
 		return 1;
 	}
+	if(m < 0) die_opt("Invalid", "\"-m\"");
+	const int et = o.pr.mark, gpus = o.gpus;
+	const double bs = o.pr.scale;
 	if((et == 2 || et == 1) && bs == 0) die_opt("Invalid", et == 2 ? "\"--short_precision\"" : "\"--byte_precision\"");
 	if(gpus < 0) die_opt("Invalid", "\"--gpus\"");
 	if(gpus && (m == CCG_TREE_CF || m == CCG_TREE_FF || m == CCG_TREE_MN)) {
-		fprintf(stderr, "ccphylo_amd: --gpus with tree method \"%s\" is not supported: the sharded engine runs nj, dnj and hnj.\n", method);
+		fprintf(stderr, "ccphylo_amd: --gpus with tree method \"%s\" is not supported: the sharded engine runs nj, dnj and hnj.\n", o.method);
 		return 1;
 	}
-	if(cmpname && (gpus || et == 2 || et == 1)) {
+	if(o.cmpname && (gpus || et == 2 || et == 1)) {
 		fprintf(stderr, "ccphylo_amd: tree --phycmp with %s is not implemented.\n", gpus ? "--gpus" : "short / byte precision (-s / -b)");
 		return 1;
 	}
 
-	FILE *out = (outname[0] == '-' && outname[1] == 0) ? stdout : fopen(outname, "wb");
-	if(!out) {
-		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-		return errno ? errno : 1;
-	}
-	ccq_reader *r = ccq_open(in);
-	if(!r) {
-		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-		return errno ? errno : 1;
-	}
+	FILE *out = open_out(o.outname);
+	if(!out) return errno_fail(1);
+	ccq_reader *r = ccq_open(o.in);
+	if(!r) return errno_fail(1);
 	FILE *cmp = NULL;
-	if(cmpname && !(cmp = fopen(cmpname, "wb"))) {
-		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-		return errno ? errno : 1;
-	}
+	if(o.cmpname && !(cmp = fopen(o.cmpname, "wb"))) return errno_fail(1);
 	ccg_ctx *ctx = NULL;
 	ccq_ltd *D = ccq_ltd_new(32, et, bs);        /* tree.c:52 */
 	ccq_names *T = ccq_names_new(32, 4);         /* tree.c:61-66 */
@@ -329,7 +244,7 @@ static int main_tree(int argc, char **argv) {
 	ccg_join *joins = NULL;
 	size_t jcap = 0;
 	clock_t t0 = clock(), t1;
-	while((n = ccq_load_phy(r, D, T, sep, quotes, &err)) > 0) {
+	while((n = ccq_load_phy(r, D, T, o.sep, o.quotes, &err)) > 0) {
 		t1 = clock();
 		fprintf(stderr, "# Total time used loading matrix: %.2f s.\n", (double) (t1 - t0) / 1000000);
 		t0 = t1;
@@ -337,7 +252,7 @@ static int main_tree(int argc, char **argv) {
 			taxa = malloc((size_t) n * sizeof(char *));
 			for(int i = 0; i < n; ++i) taxa[i] = strdup((char *) T->names[i]->seq);
 			if(n >= 2) {
-				if(!ctx) ctx = open_gpu(device);
+				if(!ctx) ctx = open_gpu(o.device);
 				const size_t bytes = (size_t) n * (size_t) (n - 1) / 2 * (size_t) et;
 				int mrc;
 				if((mrc = ccg_malloc(ctx, &A_dev, bytes)) || (mrc = ccg_malloc(ctx, &W_dev, bytes)) ||
@@ -352,15 +267,14 @@ static int main_tree(int argc, char **argv) {
 				jcap = n;
 				joins = realloc(joins, jcap * sizeof(ccg_join));
 			}
-			ccg_tree_args ta = {n, et, bs, m, flag, !fast, 0, 0};
+			ccg_tree_args ta = {n, et, bs, m, o.flag, !o.fast, 0, 0};
 			int nj = 0, fn = 0;
 			double fd = 0;
 			int64_t st[12 + 2 * CCG_NKSTAT];
 			memset(st, 0, sizeof(st));
-			int rc;
 			if(gpus) {
 				/* one matrix over G ranks, one thread per rank (host/mgpu.c) */
-				ccq_mgpu mc = {gpus, device, transport, -1};
+				ccq_mgpu mc = {gpus, o.device, o.transport, -1};
 				char emsg[320] = "";
 				rc = ccq_mgpu_tree(&mc, D->mat, &ta, joins, &nj, &fn, &fd, emsg, sizeof(emsg));
 				if(rc) {
@@ -368,7 +282,7 @@ static int main_tree(int argc, char **argv) {
 					return 1;
 				}
 			} else {
-				if(!ctx) ctx = open_gpu(device);
+				if(!ctx) ctx = open_gpu(o.device);
 				rc = cmp ? ccg_tree_dev(ctx, &ta, W_dev, joins, &nj, &fn, &fd, st)
 				         : ccg_tree(ctx, &ta, D->mat, joins, &nj, &fn, &fd, st);
 			}
@@ -376,13 +290,13 @@ static int main_tree(int argc, char **argv) {
 				fprintf(stderr, "ccphylo_amd: tree construction failed: %s\n", ccg_strerror(rc));
 				return 1;
 			}
-			if(stats && !gpus) {
+			if(o.stats && !gpus) {
 				fprintf(stderr, "# gpu: %d joins, %lld rows / %lld cells rescanned, %lld launches, %.3f ms\n", nj,
 				        (long long) st[0], (long long) st[1], (long long) st[2], st[3] / 1000.0);
 			}
-			ccq_replay_newick(T, n, (const ccq_join *) joins, nj, fn, fd, flag, precision);
+			ccq_replay_newick(T, n, (const ccq_join *) joins, nj, fn, fd, o.flag, o.precision);
 		} else if(n == 2) {
-			ccq_newick_pair(T, ccq_ltd_get(D, 0), precision);
+			ccq_newick_pair(T, ccq_ltd_get(D, 0), o.precision);
 		}
 		if(T->header->len) {
 			fprintf(out, ">%s%s;\n", (char *) T->header->seq, (char *) T->names[0]->seq);
@@ -394,7 +308,7 @@ static int main_tree(int argc, char **argv) {
 		t0 = t1;
 		if(cmp) {
 			fflush(out);   /* the tree is written whatever the comparison says */
-			const int bad = tree_phycmp(ctx, cmp, cmpflag, (char *) T->names[0]->seq, taxa, n, et, A_dev, W_dev);
+			const int bad = tree_phycmp(ctx, &o, cmp, (char *) T->names[0]->seq, taxa, n, A_dev, W_dev);
 			for(int i = 0; i < n; ++i) free(taxa[i]);
 			free(taxa);
 			if(A_dev) ccg_free(ctx, A_dev);
@@ -418,132 +332,70 @@ static int main_tree(int argc, char **argv) {
 }
 
 /* ============================================================== dbscan */
-static int dbscan_help(FILE *out) {
-	fprintf(out, "#CCPhylo make a DBSCAN given a set of phylip distance matrices.\n");
-	fprintf(out, "#   %-24s\t%-32s\t%s\n", "Options are:", "Desc:", "Default:");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'i', "input", "Input file", "stdin");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'o', "output", "Output file", "stdout");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'S', "separator", "Separator", "\\t");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'q', "quotes", "Quote taxa", "\\0");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'N', "min_neighbors", "Minimum neighbors", "1");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'e', "max_distance", "Maximum distance", "10.0");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'p', "float_precision", "Float precision on distance matrix", "double");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 's', "short_precision", "Short precision on distance matrix", "double / 1e0");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'b', "byte_precision", "Byte precision on distance matrix", "double / 1e0");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'H', "mmap", "Allocate matrix on the disk", "False");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'T', "tmp", "Set directory for temporary files", "");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'h', "help", "Shows this helpmessage", "");
-	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "device", "GPU", "0");
-	return out == stderr;
-}
+typedef struct {
+	const char *in, *outname;
+	int device, minN;
+	cli_prec pr;   /* etype, byte scale */
+	char sep, quotes;
+	double maxDist;
+} DbscanOpts;
 
-static double opt_dnum(Args *A, const char *attached, const char *opt) {
-	char *v = opt_value(A, attached, opt), *e;
-	double x = strtod(v, &e);
-	if(*e) die_opt("Invalid", opt);
-	return x;
-}
+#define F(f) offsetof(DbscanOpts, f)
+static const cli_opt dbscan_opts[] = {
+	{'i', "input", CLI_STR, F(in), 0, "Input file", "stdin"},
+	{'o', "output", CLI_STR, F(outname), 0, "Output file", "stdout"},
+	{'S', "separator", CLI_CHAR, F(sep), 0, "Separator", "\\t"},
+	{'q', "quotes", CLI_CHAR, F(quotes), 0, "Quote taxa", "\\0"},
+	{'N', "min_neighbors", CLI_INT, F(minN), 0, "Minimum neighbors", "1"},
+	{'e', "max_distance", CLI_DBL, F(maxDist), 0, "Maximum distance", "10.0"},
+	{'p', "float_precision", CLI_FLAG, F(pr.mark), 4, "Float precision on distance matrix", "double"},
+	{'s', "short_precision", CLI_PREC, F(pr), 2, "Short precision on distance matrix", "double / 1e0"},
+	{'b', "byte_precision", CLI_PREC, F(pr), 1, "Byte precision on distance matrix", "double / 1e0"},
+	{'H', "mmap", CLI_IGNORE, 0, 0, "Allocate matrix on the disk", "False"},   /* host memory knob: no effect on HBM */
+	{'T', "tmp", CLI_DROP, 0, 0, "Set directory for temporary files", ""},
+	{'h', "help", CLI_HELP, 0, 0, "Shows this helpmessage", ""},
+	{0, "device", CLI_INT, F(device), 0, "GPU", "0"},
+	{0}};
+static const cli_cmd dbscan_cmd = {"#CCPhylo make a DBSCAN given a set of phylip distance matrices.", dbscan_opts,
+                                   UNKNOWN_CMDLINE, EXTRA_CMDLINE, 1, 0, F(in)};
+#undef F
 
 /* dbscan.c:267 main_dbscan / :181 make_dbscan: every matrix of the input
  * through ccg_dbscan, printed by ccq_print_dbscan */
 static int main_dbscan(int argc, char **argv) {
-	const char *in = "-", *outname = "-";
-	int et = 8, device = 0, minN = 1;
-	char sep = '\t', quotes = 0;
-	double bs = 1.0, maxDist = 10.0;
-	Args A = {argc, 0, argv};
-	for(A.k = 1; A.k < argc; ++A.k) {
-		char *a = argv[A.k];
-		if(a[0] != '-' || a[1] == 0) {
-			in = a;
-			if(A.k + 1 < argc) {
-				fprintf(stderr, "Unexpected non-option argument(s).\n");
-				return 1;
-			}
-			break;
-		}
-		if(a[1] == '-') {
-			char *name = a + 2, *eq = strchr(name, '=');
-			char *att = NULL;
-			if(eq) {
-				*eq = 0;
-				att = eq + 1;
-			}
-			if(*name == 0) { continue; }
-			else if(!strcmp(name, "input")) in = opt_value(&A, att, "input");
-			else if(!strcmp(name, "output")) outname = opt_value(&A, att, "output");
-			else if(!strcmp(name, "separator")) sep = opt_value(&A, att, "separator")[0];
-			else if(!strcmp(name, "quotes")) quotes = opt_value(&A, att, "quotes")[0];
-			else if(!strcmp(name, "min_neighbors")) minN = (int) opt_num(&A, att, "min_neighbors");
-			else if(!strcmp(name, "max_distance")) maxDist = opt_dnum(&A, att, "max_distance");
-			else if(!strcmp(name, "float_precision")) et = 4;
-			else if(!strcmp(name, "short_precision")) { et = 2; bs = opt_dvalue_def(&A, att, bs, "short_precision"); }
-			else if(!strcmp(name, "byte_precision")) { et = 1; bs = opt_dvalue_def(&A, att, bs, "byte_precision"); }
-			else if(!strcmp(name, "mmap")) { /* host memory knob: no effect on HBM */ }
-			else if(!strcmp(name, "tmp")) (void) opt_value(&A, att, "tmp");
-			else if(!strcmp(name, "device")) device = (int) opt_num(&A, att, "device");
-			else if(!strcmp(name, "help")) return dbscan_help(stdout);
-			else die_opt("Unknown", a);
-			continue;
-		}
-		for(char *p = a + 1; *p; ++p) {
-			char o = *p, *att = p + 1;
-			int took = 1;
-			switch(o) {
-				case 'i': in = opt_value(&A, att, "i"); break;
-				case 'o': outname = opt_value(&A, att, "o"); break;
-				case 'S': sep = opt_value(&A, att, "S")[0]; break;
-				case 'q': quotes = opt_value(&A, att, "q")[0]; break;
-				case 'N': minN = (int) opt_num(&A, att, "N"); break;
-				case 'e': maxDist = opt_dnum(&A, att, "e"); break;
-				case 'T': (void) opt_value(&A, att, "T"); break;
-				case 's': et = 2; bs = opt_dvalue_def(&A, att, bs, "s"); break;
-				case 'b': et = 1; bs = opt_dvalue_def(&A, att, bs, "b"); break;
-				case 'p': et = 4; took = 0; break;
-				case 'H': took = 0; break;
-				case 'h': return dbscan_help(stdout);
-				default: {
-					char bad[3] = {'-', o, 0};
-					die_opt("Unknown", bad);
-				}
-			}
-			if(took) break;
-		}
-	}
+	DbscanOpts o = {.in = "-", .outname = "-", .minN = 1, .pr = {8, 1.0}, .sep = '\t', .maxDist = 10.0};
+	int rc = cli_parse(&dbscan_cmd, argc, argv, &o);
+	if(rc != CLI_GO) return rc;
+	const int et = o.pr.mark;
+	const double bs = o.pr.scale;
 	if((et == 2 || et == 1) && bs == 0) die_opt("Invalid", et == 2 ? "\"--short_precision\"" : "\"--byte_precision\"");
-	FILE *out = (outname[0] == '-' && outname[1] == 0) ? stdout : fopen(outname, "wb");
-	if(!out) {
-		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-		return errno ? errno : 1;
-	}
-	ccq_reader *r = ccq_open(in);
-	if(!r) {
-		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-		return errno ? errno : 1;
-	}
+	FILE *out = open_out(o.outname);
+	if(!out) return errno_fail(1);
+	ccq_reader *r = ccq_open(o.in);
+	if(!r) return errno_fail(1);
 	ccg_ctx *ctx = NULL;
 	ccq_ltd *D = ccq_ltd_new(32, et, bs);
 	ccq_names *T = ccq_names_new(32, 4);
 	int32_t *N = NULL;
 	char **names = NULL;
 	int err = 0, n, cap = 0;
-	while((n = ccq_load_phy(r, D, T, sep, quotes, &err)) > 0) {
+	while((n = ccq_load_phy(r, D, T, o.sep, o.quotes, &err)) > 0) {
 		if(cap < n) {
 			cap = n;
 			N = realloc(N, 2 * (size_t) cap * sizeof(int32_t));
 			names = realloc(names, (size_t) cap * sizeof(char *));
 		}
-		if(!ctx) ctx = open_gpu(device);
-		ccg_dbscan_args da = {n, et, bs, maxDist, minN};
+		if(!ctx) ctx = open_gpu(o.device);
+		ccg_dbscan_args da = {n, et, bs, o.maxDist, o.minN};
 		int nclust = 0;
-		int rc = ccg_dbscan(ctx, &da, D->mat, N, N + cap, &nclust, NULL);
+		rc = ccg_dbscan(ctx, &da, D->mat, N, N + cap, &nclust, NULL);
 		if(rc) {
 			fprintf(stderr, "ccphylo_amd: dbscan failed: %s\n", ccg_strerror(rc));
 			return 1;
 		}
 		for(int i = 0; i < n; ++i) names[i] = (char *) T->names[i]->seq;
-		ccq_print_dbscan(out, T->header->len ? (char *) T->header->seq : NULL, names, N, N + cap, n, nclust, maxDist,
-		                 minN);
+		ccq_print_dbscan(out, T->header->len ? (char *) T->header->seq : NULL, names, N, N + cap, n, nclust,
+		                 o.maxDist, o.minN);
 	}
 	if(out != stdout) fclose(out);
 	else fflush(stdout);
@@ -559,54 +411,78 @@ static int main_dbscan(int argc, char **argv) {
 /* ================================================================ dist */
 /* --tree_method of the fused pipelines (dist --tree, tsv2phy --tree) -> CCG_TREE_*; -1 with a message */
 static int fused_tree_method(const char *tmethod) {
-	if(!strcmp(tmethod, "dnj")) return CCG_TREE_DNJ;
-	if(!strcmp(tmethod, "nj")) return CCG_TREE_NJ;
-	if(!strcmp(tmethod, "hnj")) return CCG_TREE_HNJ;
-	if(!strcmp(tmethod, "cf")) return CCG_TREE_CF;
-	if(!strcmp(tmethod, "ff")) return CCG_TREE_FF;
-	if(!strcmp(tmethod, "mn")) return CCG_TREE_MN;
-	fprintf(stderr, "ccphylo_amd: --tree_method %s: the fused pipeline runs nj, cf, ff, mn, hnj and dnj.\n", tmethod);
-	return -1;
+	const int m = tree_method_id(tmethod);
+	if(m < 0) fprintf(stderr, "ccphylo_amd: --tree_method %s: the fused pipeline runs nj, cf, ff, mn, hnj and dnj.\n", tmethod);
+	return m;
 }
 
 /* the tail of a fused run: the engine's joins replayed over the names T holds
  * (ccq_names_set), the Newick line written and the file closed */
-static void fused_write_newick(FILE *tout, ccq_names *T, int n, const ccg_join *joins, int nj, int fn, double fd,
-                               int tflag, int precision) {
-	ccq_replay_newick(T, n, (const ccq_join *) joins, nj, fn, fd, tflag, precision);
+typedef struct {
+	const ccg_join *joins;
+	int nj, fn;
+	double fd;
+} Joins;
+
+static void fused_write_newick(FILE *tout, ccq_names *T, int n, const Joins *J, int tflag, int precision) {
+	ccq_replay_newick(T, n, (const ccq_join *) J->joins, J->nj, J->fn, J->fd, tflag, precision);
 	fprintf(tout, "%s;\n", (char *) T->names[0]->seq);
 	if(tout != stdout) fclose(tout);
 }
 
-static int dist_help(FILE *out) {
-	fprintf(out, "#CCPhylo dist calculates distances between samples based on overlaps between nucleotide count matrices created by e.g. KMA.\n");
-	fprintf(out, "#   %-24s\t%-32s\t%s\n", "Options are:", "Desc:", "Default:");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'i', "input", "Input file(s)", "stdin");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'o', "output", "Output file", "stdout");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'n', "nucleotide_numbers", "Output number of nucleotides included", "False/None");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'x', "print_precision", "Floating point print precision", "9");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'y', "methylation_motifs", "Mask methylation motifs from <file>", "False/None");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'L', "min_len", "Minimum overlapping length", "1");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'C', "min_cov", "Minimum coverage", "50.0%");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'W', "normalization_weight", "Normalization weight", "0 / None");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'P', "proximity", "Minimum proximity between SNPs", "0");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'f', "flag", "Output flags", "1");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'F', "flag_help", "Help on option \"-f\"", "");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'p', "float_precision", "Float precision on distance matrix", "double");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 's', "short_precision", "Short precision on distance matrix", "double / 1e0");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'b', "byte_precision", "Byte precision on distance matrix", "double / 1e0");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 't', "threads", "Number of threads", "1");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'h', "help", "Shows this helpmessage", "");
-	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "tree", "Also build the tree in HBM, Newick to FILE", "off");
-	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "dbscan", "Also cluster in HBM, table to FILE", "off");
-	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "max_distance", "dbscan -e for --dbscan", "10.0");
-	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "min_neighbors", "dbscan -N for --dbscan", "1");
-	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "tree_method", "nj / cf / ff / mn / hnj / dnj for --tree", "dnj");
-	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "tree_flag", "tree -f flags for --tree", "0");
-	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "gpus", "Shard --tree over G GPUs", "1");
-	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "transport", "rccl / host collectives for --gpus", "rccl");
-	return out == stderr;
-}
+typedef struct {
+	cli_list files;
+	const char *outname, *noutname, *treename, *tmethod, *dbname, *unsup, *tmpl, *method, *methname;
+	double maxDist, minCov;
+	int minN, precision, device, gpus, transport, fast, tflag;
+	unsigned flag, norm, minLength, proxi, minDepth, threads;
+	cli_prec pr;   /* etype, byte scale */
+} DistOpts;
+
+#define F(f) offsetof(DistOpts, f)
+static const cli_opt dist_opts[] = {
+	{'i', "input", CLI_LIST, F(files), 0, "Input file(s)", "stdin"},
+	{'o', "output", CLI_STR, F(outname), 0, "Output file", "stdout"},
+	{'n', "nucleotide_numbers", CLI_STR, F(noutname), 0, "Output number of nucleotides included", "False/None"},
+	{'x', "print_precision", CLI_INT, F(precision), 0, "Floating point print precision", "9"},
+	{'y', "methylation_motifs", CLI_STR, F(methname), 0, "Mask methylation motifs from <file>", "False/None"},
+	{'L', "min_len", CLI_INT, F(minLength), 0, "Minimum overlapping length", "1"},
+	{'C', "min_cov", CLI_PCT, F(minCov), 0, "Minimum coverage", "50.0%"},
+	{'W', "normalization_weight", CLI_INT, F(norm), 0, "Normalization weight", "0 / None"},
+	{'P', "proximity", CLI_INT, F(proxi), 0, "Minimum proximity between SNPs", "0"},
+	{'f', "flag", CLI_INT, F(flag), 0, "Output flags", "1"},
+	{'F', "flag_help", CLI_FLAG, F(flag), -1, "Help on option \"-f\"", ""},
+	{'p', "float_precision", CLI_FLAG, F(pr.mark), 4, "Float precision on distance matrix", "double"},
+	{'s', "short_precision", CLI_PREC, F(pr), 2, "Short precision on distance matrix", "double / 1e0"},
+	{'b', "byte_precision", CLI_PREC, F(pr), 1, "Byte precision on distance matrix", "double / 1e0"},
+	{'t', "threads", CLI_INT, F(threads), 0, "Number of threads", "1"},
+	{'h', "help", CLI_HELP, 0, 0, "Shows this helpmessage", ""},
+	{0, "tree", CLI_STR, F(treename), 0, "Also build the tree in HBM, Newick to FILE", "off"},
+	{0, "dbscan", CLI_STR, F(dbname), 0, "Also cluster in HBM, table to FILE", "off"},
+	{0, "max_distance", CLI_DBL, F(maxDist), 0, "dbscan -e for --dbscan", "10.0"},
+	{0, "min_neighbors", CLI_INT, F(minN), 0, "dbscan -N for --dbscan", "1"},
+	{0, "tree_method", CLI_STR, F(tmethod), 0, "nj / cf / ff / mn / hnj / dnj for --tree", "dnj"},
+	{0, "tree_flag", CLI_INT, F(tflag), 0, "tree -f flags for --tree", "0"},
+	{0, "gpus", CLI_INT, F(gpus), 0, "Shard --tree over G GPUs", "1"},
+	{0, "transport", CLI_ENUM, F(transport), 0, "rccl / host collectives for --gpus", "rccl", 0, transports},
+	/* the reference's options that its help does not list either, and this engine's own */
+	{'d', "distance", CLI_STR, F(method)},
+	{'D', "distance_help", CLI_UNSET, F(method)},
+	{'r', "reference", CLI_STR, F(tmpl)},
+	{'E', "min_depth", CLI_UDBL, F(minDepth)},
+	{'l', "significance_lvl", CLI_DROP},
+	{'S', "separator", CLI_DROP},
+	{'T', "tmp", CLI_DROP},
+	{'H', "mmap", CLI_IGNORE},
+	{'a', "add", CLI_UNSUP, F(unsup)},
+	{'V', "nucleotide_variations", CLI_UNSUP, F(unsup)},
+	{0, "device", CLI_INT, F(device)},
+	{0, "fast_sums", CLI_FLAG, F(fast), 1},
+	{0}};
+/* a bare `--` is an unknown option here, and the trailing words are the input list (dist.c:565) */
+static const cli_cmd dist_cmd = {"#CCPhylo dist calculates distances between samples based on overlaps between nucleotide count matrices created by e.g. KMA.",
+                                 dist_opts, UNKNOWN_CMDLINE, NULL, 0, 1, F(files)};
+#undef F
 
 /* dist.c:736-790: -d name -> metric; z, p, np -> -1 (not on the GPU engine) */
 static int kma_metric_id(const char *m, int *id, unsigned *lnorm) {
@@ -648,45 +524,34 @@ static int first_byte(const char *path) {
 
 /* dist.c:138-180 with count matrices: ltdMatrixThrd's samples, cmpMats per
  * pair on the GPU (ccg_kma_ltd), printphy of D (and N) */
-static int dist_kma(char **files, int nfiles, const char *tmpl, const char *outname, const char *noutname,
-                    int metric, unsigned lnorm, unsigned norm, unsigned minDepth, unsigned minLength, double minCov,
-                    unsigned flag, int precision, int et, double bs, unsigned threads, int device) {
+static int dist_kma(const DistOpts *o, int metric, unsigned lnorm) {
+	const int et = o->pr.mark;
+	const double bs = o->pr.scale;
 	if(metric < 0) {
 		fprintf(stderr, "ccphylo_amd: distance method is not implemented by the GPU engine (z, p, np).\n");
 		return 1;
 	}
-	FILE *out = (outname[0] == '-' && outname[1] == 0) ? stdout : fopen(outname, "wb");
-	if(!out) {
-		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-		return 1;
-	}
+	FILE *out = open_out(o->outname);
+	if(!out) return errno_fail(0);
 	FILE *nout = NULL;
-	if(noutname) {
-		if(!strcmp(noutname, outname)) nout = out;
-		else if(noutname[0] == '-' && noutname[1] == 0) nout = stdout;
-		else nout = fopen(noutname, "wb");
-		if(!nout) {
-			fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-			return 1;
-		}
-	}
-	ccq_kma *K = ccq_load_kma(files, nfiles, tmpl, minDepth, minLength, minCov, threads > 16 ? (int) threads : 16,
-	                          stderr);
+	if(o->noutname && !(nout = open_nout(o->noutname, o->outname, out))) return errno_fail(0);
+	ccq_kma *K = ccq_load_kma(o->files.v, o->files.n, o->tmpl, o->minDepth, o->minLength, o->minCov,
+	                          o->threads > 16 ? (int) o->threads : 16, stderr);
 	if(K->status) return 1;
 	const int n = K->n;
 	ccq_ltd *D = ccq_ltd_new(n > 1 ? n : 2, et, bs), *N = ccq_ltd_new(n > 1 ? n : 2, et, bs);
 	D->n = N->n = 0;
 	if(n > 1) {
-		ccg_ctx *ctx = open_gpu(device);
+		ccg_ctx *ctx = open_gpu(o->device);
 		ccg_kma_args a;
 		memset(&a, 0, sizeof(a));
 		a.n = n;
 		a.metric = metric;
 		a.lnorm = lnorm;
-		a.norm = norm;
-		a.minDepth = minDepth;
-		a.minLength = minLength;
-		a.minCov = minCov;
+		a.norm = o->norm;
+		a.minDepth = o->minDepth;
+		a.minLength = o->minLength;
+		a.minCov = o->minCov;
 		a.etype = et;
 		a.byteScale = bs;
 		a.stride1 = K->stride1;
@@ -706,16 +571,16 @@ static int dist_kma(char **files, int nfiles, const char *tmpl, const char *outn
 			int64_t i = 1;
 			while((i + 1) * i / 2 <= fatal) ++i;
 			const int64_t j = fatal - i * (i - 1) / 2;
-			fprintf(stderr, "Template (\"%s\") did not exceed threshold for inclusion:\t%s\n", tmpl,
-			        files[K->file_of[j]]);
+			fprintf(stderr, "Template (\"%s\") did not exceed threshold for inclusion:\t%s\n", o->tmpl,
+			        o->files.v[K->file_of[j]]);
 			return 1;
 		}
 		if(et >= 4) {   /* cmpMatThrd's warning (it names files[row]) */
 			for(int64_t i = 1, f = 0; i < n; ++i) {
 				for(int64_t j = 0; j < i; ++j, ++f) {
 					if(ccq_ltd_get(D, f) == -1.0) {
-						fprintf(stderr, "No sufficient overlap between samples:\t%s\t%s\n", files[i],
-						        files[K->file_of[j]]);
+						fprintf(stderr, "No sufficient overlap between samples:\t%s\t%s\n", o->files.v[i],
+						        o->files.v[K->file_of[j]]);
 					}
 				}
 			}
@@ -723,8 +588,8 @@ static int dist_kma(char **files, int nfiles, const char *tmpl, const char *outn
 		D->n = N->n = n;
 	}
 	if(1 < D->n) {
-		ccq_print_phy(out, D, files, K->include, tmpl, flag, precision);
-		if(nout && 1 < N->n) ccq_print_phy(nout, N, files, K->include, tmpl, flag, precision);
+		ccq_print_phy(out, D, o->files.v, K->include, o->tmpl, o->flag, o->precision);
+		if(nout && 1 < N->n) ccq_print_phy(nout, N, o->files.v, K->include, o->tmpl, o->flag, o->precision);
 	}
 	if(out != stdout) fclose(out);
 	else fflush(stdout);
@@ -764,51 +629,44 @@ static void fsa_cell_pairs(const unsigned char *include, int n, int64_t cells, i
 }
 
 /* dist.c:138-180 with FASTA files and -r: ltdFsaMatrix_get (cdist.c:36) */
-static int dist_fsa_files(char **files, int nfiles, const char *tmpl, const char *outname, const char *noutname,
-                          unsigned flag, unsigned norm, unsigned minLength, double minCov, unsigned proxi,
-                          int precision, int et, double bs, int device) {
-	FILE *out = (outname[0] == '-' && outname[1] == 0) ? stdout : fopen(outname, "wb");
-	if(!out) {
-		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-		return 1;
-	}
-	FILE *nout = NULL;
-	if(noutname) {
-		if(!strcmp(noutname, outname)) nout = out;
-		else if(noutname[0] == '-' && noutname[1] == 0) nout = stdout;
-		else nout = fopen(noutname, "wb");
-	}
-	unsigned char *include = calloc((size_t) nfiles, 1);
-	ccq_msa *M = ccq_load_fsa_files(files, nfiles, tmpl, flag, minLength, minCov, proxi, include, stderr);
+static int dist_fsa_files(const DistOpts *o) {
+	const int et = o->pr.mark;
+	const double bs = o->pr.scale;
+	FILE *out = open_out(o->outname);
+	if(!out) return errno_fail(0);
+	FILE *nout = o->noutname ? open_nout(o->noutname, o->outname, out) : NULL;
+	unsigned char *include = calloc((size_t) o->files.n, 1);
+	ccq_msa *M = ccq_load_fsa_files(o->files.v, o->files.n, o->tmpl, o->flag, o->minLength, o->minCov, o->proxi, include,
+	                                stderr);
 	if(!M) return 1;
 	int Dn = 0;
-	for(int f = 0; f < nfiles; ++f) Dn += include[f] != 0;
+	for(int f = 0; f < o->files.n; ++f) Dn += include[f] != 0;
 	ccq_ltd *D = ccq_ltd_new(Dn > 1 ? Dn : 2, et, bs), *N = ccq_ltd_new(Dn > 1 ? Dn : 2, et, bs);
 	D->n = N->n = 0;
 	const int W = M->W;
 	if(!Dn) {
 		fprintf(stderr, "All sequences were trimmed away.\n");
 	} else {
-		ccg_ctx *ctx = open_gpu(device);
+		ccg_ctx *ctx = open_gpu(o->device);
 		ccg_snp_args sa;
 		memset(&sa, 0, sizeof(sa));
 		sa.len = M->len;
 		sa.stride = W;
 		sa.pair = M->pair;
-		sa.norm = norm;
+		sa.norm = o->norm;
 		sa.minLength = M->minLength;
-		sa.proxi = M->pair ? proxi : 0;
+		sa.proxi = M->pair ? o->proxi : 0;
 		sa.etype = et;
 		sa.byteScale = bs;
 		int rc = CCG_OK;
 		if(!M->pair) {
 			fprintf(stderr, "# %d / %d bases included in distance matrix.\n", ccq_npos(M->incs, M->len), M->len);
 		}
-		if(M->pair || Dn == nfiles) {
+		if(M->pair || Dn == o->files.n) {
 			/* pairs of included files in order (cmpairFsaThrd skips with `||`) */
 			uint64_t *sq = malloc((size_t) Dn * W * 8);
 			uint32_t *ic = malloc((size_t) (M->pair ? Dn : 1) * W * 4);
-			for(int f = 0, r = 0; f < nfiles; ++f) {
+			for(int f = 0, r = 0; f < o->files.n; ++f) {
 				if(!include[f]) continue;
 				memcpy(sq + (size_t) r * W, M->seqs + (size_t) f * W, (size_t) W * 8);
 				if(M->pair) memcpy(ic + (size_t) r * W, M->incs + (size_t) f * W, (size_t) W * 4);
@@ -823,14 +681,14 @@ static int dist_fsa_files(char **files, int nfiles, const char *tmpl, const char
 			free(ic);
 		} else if(Dn > 1) {
 			/* all files, then the cells in cmpFsaThrd's quirky pair order */
-			ccq_ltd *F = ccq_ltd_new(nfiles, et, bs);
-			sa.n = nfiles;
+			ccq_ltd *F = ccq_ltd_new(o->files.n, et, bs);
+			sa.n = o->files.n;
 			sa.seqs = M->seqs;
 			sa.incs = M->incs;
 			rc = ccg_snp_ltd(ctx, &sa, F->mat, NULL, NULL);
 			const int64_t cells = (int64_t) Dn * (Dn - 1) / 2;
 			int *pi_ = malloc((size_t) cells * sizeof(int)), *pj_ = malloc((size_t) cells * sizeof(int));
-			fsa_cell_pairs(include, nfiles, cells, pi_, pj_);
+			fsa_cell_pairs(include, o->files.n, cells, pi_, pj_);
 			for(int64_t c = 0; c < cells; ++c) {
 				const int64_t src = (int64_t) pi_[c] * (pi_[c] - 1) / 2 + pj_[c];
 				memcpy((char *) D->mat + c * et, (char *) F->mat + src * et, (size_t) et);
@@ -848,8 +706,8 @@ static int dist_fsa_files(char **files, int nfiles, const char *tmpl, const char
 		if(M->pair) N->n = Dn;
 	}
 	if(1 < D->n) {
-		ccq_print_phy(out, D, files, include, tmpl, flag, precision);
-		if(nout && 1 < N->n) ccq_print_phy(nout, N, files, include, tmpl, flag, precision);
+		ccq_print_phy(out, D, o->files.v, include, o->tmpl, o->flag, o->precision);
+		if(nout && 1 < N->n) ccq_print_phy(nout, N, o->files.v, include, o->tmpl, o->flag, o->precision);
 	}
 	if(out != stdout) fclose(out);
 	else fflush(stdout);
@@ -913,55 +771,48 @@ static int apply_motifs(ccq_msa *M, const ccq_motif *mo, int nmo, int device) {
  * -W normalised distances are rounded to -x digits as the text would round
  * them (ccg_round_decimal_dev), taxon names as that pipeline's reader holds
  * them (ccq_names_set). */
-static int dist_tree(const char *in, const char *treename, const char *tmethod, int tflag, unsigned flag,
-                     unsigned norm, unsigned minLength, double minCov, unsigned proxi, int precision, int et,
-                     double bs, unsigned threads, int device, int gpus, int transport, int fast,
-                     const char *dbname, double maxDist, int minN, const char *methname) {
-	const int m = fused_tree_method(tmethod);
+static int dist_tree(const DistOpts *o) {
+	const int et = o->pr.mark;
+	const double bs = o->pr.scale;
+	const int m = fused_tree_method(o->tmethod);
 	if(m < 0) return 1;
-	if(gpus > 1 && (m == CCG_TREE_CF || m == CCG_TREE_FF || m == CCG_TREE_MN)) {
-		fprintf(stderr, "ccphylo_amd: --gpus with --tree_method %s is not supported: the sharded engine runs nj, dnj and hnj.\n", tmethod);
+	if(o->gpus > 1 && (m == CCG_TREE_CF || m == CCG_TREE_FF || m == CCG_TREE_MN)) {
+		fprintf(stderr, "ccphylo_amd: --gpus with --tree_method %s is not supported: the sharded engine runs nj, dnj and hnj.\n", o->tmethod);
 		return 1;
 	}
-	if(treename && norm && (et == 2 || et == 1)) {
+	if(o->treename && o->norm && (et == 2 || et == 1)) {
 		/* the pipeline's text round trip of -W cells through dtouc is not restated */
 		fprintf(stderr, "ccphylo_amd: -W with -s / -b and --tree: use `ccphylo dist ... | ccphylo tree`.\n");
 		return 1;
 	}
-	if(dbname && gpus > 1) {
+	if(o->dbname && o->gpus > 1) {
 		fprintf(stderr, "ccphylo_amd: --gpus with --dbscan is not supported: the clustering runs on one GPU.\n");
 		return 1;
 	}
-	if(dbname && (et == 2 || et == 1) && (norm || bs != 1.0)) {
+	if(o->dbname && (et == 2 || et == 1) && (o->norm || bs != 1.0)) {
 		/* scaled or -W cells: the pipeline's text round trip through dtouc is not restated */
 		fprintf(stderr, "ccphylo_amd: -s / -b with a scale or -W and --dbscan is not supported: use `ccphylo dist ... | ccphylo dbscan`.\n");
 		return 1;
 	}
 	FILE *tout = NULL, *dout = NULL;
-	if(treename) tout = (treename[0] == '-' && treename[1] == 0) ? stdout : fopen(treename, "wb");
-	if(dbname) dout = (dbname[0] == '-' && dbname[1] == 0) ? stdout : fopen(dbname, "wb");
-	if((treename && !tout) || (dbname && !dout)) {
-		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-		return 1;
-	}
-	ccq_reader *r = ccq_open(in);
-	if(!r) {
-		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-		return 1;
-	}
+	if(o->treename) tout = open_out(o->treename);
+	if(o->dbname) dout = open_out(o->dbname);
+	if((o->treename && !tout) || (o->dbname && !dout)) return errno_fail(0);
+	ccq_reader *r = ccq_open(o->files.n ? o->files.v[0] : "-");
+	if(!r) return errno_fail(0);
 	if(ccq_peek(r) != '>') {
 		fprintf(stderr, "ccphylo_amd: --tree / --dbscan need an MSA (FASTA) input.\n");
 		return 1;
 	}
 	ccq_motif *mo = NULL;
-	const int nmo = methname ? load_motifs_or_die(methname, &mo) : 0;
-	ccq_msa *M = ccq_load_msa_par_meth(r, flag, minLength, minCov, proxi, threads > 16 ? (int) threads : 16, mo, nmo,
-	                                   stderr);
+	const int nmo = o->methname ? load_motifs_or_die(o->methname, &mo) : 0;
+	ccq_msa *M = ccq_load_msa_par_meth(r, o->flag, o->minLength, o->minCov, o->proxi,
+	                                   o->threads > 16 ? (int) o->threads : 16, mo, nmo, stderr);
 	ccq_close(r);
-	if(apply_motifs(M, mo, nmo, device)) return 1;
+	if(apply_motifs(M, mo, nmo, o->device)) return 1;
 	free(mo);
 	const int n = M->n;
-	if(treename && n < 3) {
+	if(o->treename && n < 3) {
 		fprintf(stderr, "ccphylo_amd: --tree needs at least 3 included sequences (%d).\n", n);
 		return 1;
 	}
@@ -979,29 +830,29 @@ static int dist_tree(const char *in, const char *treename, const char *tmethod, 
 	sa.seqs = M->seqs;
 	sa.incs = M->incs;
 	sa.pair = M->pair;   /* -f 2: per-taxon masks, fsacmpair per cell (and -P maskProxi) */
-	sa.proxi = M->pair ? proxi : 0;
-	sa.norm = norm;
+	sa.proxi = M->pair ? o->proxi : 0;
+	sa.norm = o->norm;
 	sa.minLength = M->minLength;
 	sa.etype = et;
 	sa.byteScale = bs;
-	ccg_tree_args ta = {n, et, bs, m, tflag, !fast, 0, 0};
+	ccg_tree_args ta = {n, et, bs, m, o->tflag, !o->fast, 0, 0};
 	ccg_join *joins = malloc((size_t) n * sizeof(ccg_join));
-	ccg_dbscan_args da = {n, et, bs, maxDist, minN};
-	int32_t *dbN = dbname ? malloc(2 * (size_t) n * sizeof(int32_t)) : NULL;
+	ccg_dbscan_args da = {n, et, bs, o->maxDist, o->minN};
+	int32_t *dbN = o->dbname ? malloc(2 * (size_t) n * sizeof(int32_t)) : NULL;
 	int nclust = 0;
 	int nj = 0, fn = 0, inc = 0;
 	double fd = 0;
 	/* -W distances are not integral: the Phylip text of `dist | tree` rounds
 	 * them to -x digits, and so does this path (ccg_round_decimal_dev) */
-	const int rp = norm ? precision : -1;
+	const int rp = o->norm ? o->precision : -1;
 	char emsg[320] = "";
 	clock_t t0 = clock();
 	int rc;
-	if(gpus <= 1) {
+	if(o->gpus <= 1) {
 		/* one GPU: the full LT (the world-1 band layout) and the single-GPU
 		 * engine, which also runs the missing-entry rules of updateD
 		 * (nj.c:1021-1030) and -m hnj, exactly as `dist | tree` would */
-		ccg_ctx *ctx = open_gpu(device);
+		ccg_ctx *ctx = open_gpu(o->device);
 		void *dD = NULL;
 		const size_t lt = (size_t) n * (size_t) (n - 1) / 2 * (size_t) et;
 		if((rc = ccg_malloc(ctx, &dD, lt))) snprintf(emsg, sizeof(emsg), "LT buffer: %s", ccg_strerror(rc));
@@ -1010,36 +861,36 @@ static int dist_tree(const char *in, const char *treename, const char *tmethod, 
 		else if(rp >= 0 && (rc = ccg_round_decimal_dev(ctx, dD, (int64_t) n * (n - 1) / 2, et, rp)))
 			snprintf(emsg, sizeof(emsg), "ccg_round_decimal_dev: %s", ccg_strerror(rc));
 		/* round, then cluster, then the tree: it consumes the buffer, ccg_dbscan_dev only reads it */
-		else if(dbname && (rc = ccg_dbscan_dev(ctx, &da, dD, dbN, dbN + n, &nclust, NULL)))
+		else if(o->dbname && (rc = ccg_dbscan_dev(ctx, &da, dD, dbN, dbN + n, &nclust, NULL)))
 			snprintf(emsg, sizeof(emsg), "ccg_dbscan_dev: %s", ccg_strerror(rc));
-		else if(treename && (rc = ccg_tree_dev(ctx, &ta, dD, joins, &nj, &fn, &fd, NULL)))
+		else if(o->treename && (rc = ccg_tree_dev(ctx, &ta, dD, joins, &nj, &fn, &fd, NULL)))
 			snprintf(emsg, sizeof(emsg), "ccg_tree_dev: %s", ccg_strerror(rc));
 		if(dD) ccg_free(ctx, dD);
 		ccg_destroy(ctx);
 	} else {
-		ccq_mgpu mc = {gpus, device, transport, rp};
+		ccq_mgpu mc = {o->gpus, o->device, o->transport, rp};
 		rc = ccq_mgpu_dist_tree(&mc, &sa, &ta, joins, &nj, &fn, &fd, &inc, emsg, sizeof(emsg));
 		if(rc == CCG_EUNSUP)
 			fprintf(stderr, "ccphylo_amd: the matrix has missing entries (pairs below the minimum length); "
 			                "their updateD rules run on one GPU: use --gpus 1.\n");
 	}
 	if(rc) {
-		fprintf(stderr, "ccphylo_amd: dist --%s failed: %s\n", treename ? "tree" : "dbscan", emsg);
+		fprintf(stderr, "ccphylo_amd: dist --%s failed: %s\n", o->treename ? "tree" : "dbscan", emsg);
 		return 1;
 	}
-	fprintf(stderr, "# Total time used computing distances and %s: %.2f s.\n", treename ? "tree" : "clusters",
+	fprintf(stderr, "# Total time used computing distances and %s: %.2f s.\n", o->treename ? "tree" : "clusters",
 	        (double) (clock() - t0) / 1000000);
 	ccq_names *T = ccq_names_new(32, 4);   /* as tree.c:61-66 */
-	ccq_names_set(T, M->headers, n, flag, '\t');
-	if(dbname) {   /* before the replay, which edits the names */
+	ccq_names_set(T, M->headers, n, o->flag, '\t');
+	if(o->dbname) {   /* before the replay, which edits the names */
 		char **names = malloc((size_t) n * sizeof(char *));
 		for(int i = 0; i < n; ++i) names[i] = (char *) T->names[i]->seq;
-		ccq_print_dbscan(dout, NULL, names, dbN, dbN + n, n, nclust, maxDist, minN);
+		ccq_print_dbscan(dout, NULL, names, dbN, dbN + n, n, nclust, o->maxDist, o->minN);
 		free(names);
 		if(dout != stdout) fclose(dout);
 		free(dbN);
 	}
-	if(treename) fused_write_newick(tout, T, n, joins, nj, fn, fd, tflag, precision);
+	if(o->treename) fused_write_newick(tout, T, n, &(Joins){joins, nj, fn, fd}, o->tflag, o->precision);
 	fflush(stdout);
 	ccq_names_free(T);
 	free(joins);
@@ -1047,140 +898,89 @@ static int dist_tree(const char *in, const char *treename, const char *tmethod, 
 	return 0;
 }
 
-static int main_dist(int argc, char **argv) {
-	const char *outname = "-", *noutname = NULL, *treename = NULL, *tmethod = "dnj", *dbname = NULL;
-	double maxDist = 10.0;
-	int minN = 1;
-	char **files = NULL;
-	int nfiles = 0, precision = 9, et = 8, device = 0, gpus = 0, transport = CCQ_TRANSPORT_RCCL, fast = 0, tflag = 0;
-	unsigned flag = 1, norm = 0, minLength = 1, proxi = 0, minDepth = 15, threads = 1;
-	double minCov = 0.5, bs = 1.0;
-	const char *unsup = NULL, *tmpl = NULL, *method = "cos", *methname = NULL;
-	Args A = {argc, 0, argv};
-	for(A.k = 1; A.k < argc; ++A.k) {
-		char *a = argv[A.k];
-		if(a[0] != '-' || a[1] == 0) {
-			files = argv + A.k;
-			nfiles = argc - A.k;
-			break;
-		}
-		if(a[1] == '-') {
-			char *name = a + 2, *eq = strchr(name, '=');
-			char *att = NULL;
-			if(eq) {
-				*eq = 0;
-				att = eq + 1;
-			}
-			if(!strcmp(name, "input")) {
-				if(att) {
-					files = &argv[A.k];
-					argv[A.k] = att;
-					nfiles = 1;
-				} else {
-					files = argv + A.k + 1;
-					nfiles = 0;
-				}
-				while(A.k + 1 < argc && (argv[A.k + 1][0] != '-' || argv[A.k + 1][1] == 0)) {
-					++A.k;
-					++nfiles;
-				}
-			}
-			else if(!strcmp(name, "output")) outname = opt_value(&A, att, "output");
-			else if(!strcmp(name, "nucleotide_numbers")) noutname = opt_value(&A, att, "nucleotide_numbers");
-			else if(!strcmp(name, "separator")) (void) opt_value(&A, att, "separator");
-			else if(!strcmp(name, "print_precision")) precision = (int) opt_num(&A, att, "print_precision");
-			else if(!strcmp(name, "min_len")) minLength = (unsigned) opt_num(&A, att, "min_len");
-			else if(!strcmp(name, "min_cov")) minCov = strtod(opt_value(&A, att, "min_cov"), NULL) / 100;
-			else if(!strcmp(name, "normalization_weight")) norm = (unsigned) opt_num(&A, att, "normalization_weight");
-			else if(!strcmp(name, "proximity")) proxi = (unsigned) opt_num(&A, att, "proximity");
-			else if(!strcmp(name, "flag")) flag = (unsigned) opt_num(&A, att, "flag");
-			else if(!strcmp(name, "flag_help")) flag = (unsigned) -1;
-			else if(!strcmp(name, "threads")) threads = (unsigned) opt_num(&A, att, "threads");
-			else if(!strcmp(name, "float_precision")) et = 4;
-			else if(!strcmp(name, "short_precision")) { et = 2; bs = opt_dvalue_def(&A, att, bs, "short_precision"); }
-			else if(!strcmp(name, "byte_precision")) { et = 1; bs = opt_dvalue_def(&A, att, bs, "byte_precision"); }
-			else if(!strcmp(name, "mmap")) { }
-			else if(!strcmp(name, "tmp")) (void) opt_value(&A, att, "tmp");
-			else if(!strcmp(name, "device")) device = (int) opt_num(&A, att, "device");
-			else if(!strcmp(name, "tree")) treename = opt_value(&A, att, "tree");
-			else if(!strcmp(name, "dbscan")) dbname = opt_value(&A, att, "dbscan");
-			else if(!strcmp(name, "max_distance")) maxDist = opt_dnum(&A, att, "max_distance");
-			else if(!strcmp(name, "min_neighbors")) minN = (int) opt_num(&A, att, "min_neighbors");
-			else if(!strcmp(name, "tree_method")) tmethod = opt_value(&A, att, "tree_method");
-			else if(!strcmp(name, "tree_flag")) tflag = (int) opt_num(&A, att, "tree_flag");
-			else if(!strcmp(name, "gpus")) gpus = (int) opt_num(&A, att, "gpus");
-			else if(!strcmp(name, "transport")) transport = transport_id(opt_value(&A, att, "transport"));
-			else if(!strcmp(name, "fast_sums")) fast = 1;
-			else if(!strcmp(name, "distance")) method = opt_value(&A, att, name);
-			else if(!strcmp(name, "distance_help")) method = NULL;
-			else if(!strcmp(name, "min_depth")) minDepth = (unsigned) strtod(opt_value(&A, att, name), NULL);
-			else if(!strcmp(name, "significance_lvl")) (void) opt_value(&A, att, name);
-			else if(!strcmp(name, "reference")) tmpl = opt_value(&A, att, name);
-			else if(!strcmp(name, "methylation_motifs")) methname = opt_value(&A, att, name);
-			else if(!strcmp(name, "add") || !strcmp(name, "nucleotide_variations")) { (void) opt_value(&A, att, name); unsup = name; }
-			else if(!strcmp(name, "help")) return dist_help(stdout);
-			else die_opt("Unknown", a);
-			continue;
-		}
-		for(char *p = a + 1; *p; ++p) {
-			char o = *p, *att = p + 1;
-			int took = 1;
-			switch(o) {
-				case 'i':
-					if(*att) {
-						argv[A.k] = att;
-						files = argv + A.k;
-						nfiles = 1;
-					} else {
-						files = argv + A.k + 1;
-						nfiles = 0;
-					}
-					while(A.k + 1 < argc && (argv[A.k + 1][0] != '-' || argv[A.k + 1][1] == 0)) {
-						++A.k;
-						++nfiles;
-					}
-					break;
-				case 'o': outname = opt_value(&A, att, "o"); break;
-				case 'n': noutname = opt_value(&A, att, "n"); break;
-				case 'S': (void) opt_value(&A, att, "S"); break;
-				case 'x': precision = (int) opt_num(&A, att, "x"); break;
-				case 'L': minLength = (unsigned) opt_num(&A, att, "L"); break;
-				case 'C': minCov = strtod(opt_value(&A, att, "C"), NULL) / 100; break;
-				case 'W': norm = (unsigned) opt_num(&A, att, "W"); break;
-				case 'P': proxi = (unsigned) opt_num(&A, att, "P"); break;
-				case 'f': flag = (unsigned) opt_num(&A, att, "f"); break;
-				case 't': threads = (unsigned) opt_num(&A, att, "t"); break;
-				case 'T': (void) opt_value(&A, att, "T"); break;
-				case 'd': method = opt_value(&A, att, "d"); break;
-				case 'E': minDepth = (unsigned) strtod(opt_value(&A, att, "E"), NULL); break;
-				case 'l': (void) opt_value(&A, att, "l"); break;
-				case 'r': tmpl = opt_value(&A, att, "r"); break;
-				case 'y': methname = opt_value(&A, att, "y"); break;
-				case 'a': case 'V': {
-					static char nm[2];
-					nm[0] = o;
-					(void) opt_value(&A, att, nm);
-					unsup = nm;
-					break;
-				}
-				case 's': et = 2; bs = opt_dvalue_def(&A, att, bs, "s"); break;
-				case 'b': et = 1; bs = opt_dvalue_def(&A, att, bs, "b"); break;
-				case 'p': et = 4; took = 0; break;
-				case 'F': flag = (unsigned) -1; took = 0; break;
-				case 'D': method = NULL; took = 0; break;
-				case 'H': took = 0; break;
-				case 'h': return dist_help(stdout);
-				default: {
-					char bad[3] = {'-', o, 0};
-					die_opt("Unknown", bad);
-				}
-			}
-			if(took) break;
-		}
+/* one MSA: cdist.c:196 ltdMsaMatrix_get on the GPU (ccg_snp_ltd), printphy of D (and N) */
+static int dist_msa(const DistOpts *o) {
+	const int et = o->pr.mark;
+	const double bs = o->pr.scale;
+	FILE *out = open_out(o->outname);
+	if(!out) return errno_fail(0);
+	/* dist.c:74-84 opens (truncates) it; cdist.c:367 then prints N to outfile */
+	FILE *nout = o->noutname ? open_nout(o->noutname, o->outname, out) : NULL;
+	ccq_reader *r = ccq_open(o->files.n ? o->files.v[0] : "-");
+	if(!r) return errno_fail(0);
+	if(!(o->flag & 16) && ccq_peek(r) != '>') {
+		fprintf(stderr, "ccphylo_amd: count-matrix (.mat) / union input is not implemented by the GPU engine.\n");
+		return 1;
 	}
-	if(minCov < 0 || 1 < minCov) die_opt("Invalid", "\"--min_cov\"");
-	if(bs == 0) die_opt("Invalid", et == 2 ? "\"--short_precision\"" : "\"--byte_precision\"");
-	if(flag == (unsigned) -1) {
+	/* the per-sequence work on host threads (fasta_par.c; the same result as
+	 * the serial ccq_load_msa) */
+	ccq_motif *mo = NULL;
+	const int nmo = o->methname ? load_motifs_or_die(o->methname, &mo) : 0;
+	ccq_msa *M = ccq_load_msa_par_meth(r, o->flag, o->minLength, o->minCov, o->proxi,
+	                                   o->threads > 16 ? (int) o->threads : 16, mo, nmo, stderr);
+	ccq_close(r);
+	if(apply_motifs(M, mo, nmo, o->device)) return 1;
+	free(mo);
+	int n = M->n;
+	if(n * (n - 1) / 2 < 1) {
+		fprintf(stderr, "Adjustning number of nodes to %d, to conform with the matrix size.\n", n * (n - 1) / 2);
+	}
+	ccq_ltd *D = ccq_ltd_new(n > 1 ? n : 2, et, bs), *N = NULL;
+	if(!n) {
+		fprintf(stderr, "All sequences were trimmed away.\n");
+		D->n = 0;
+	} else {
+		if(o->noutname) N = ccq_ltd_new(n > 1 ? n : 2, et, bs);
+		ccg_ctx *ctx = open_gpu(o->device);
+		ccg_snp_args sa;
+		memset(&sa, 0, sizeof(sa));
+		sa.n = n;
+		sa.len = M->len;
+		sa.stride = M->W;
+		sa.seqs = M->seqs;
+		sa.incs = M->incs;
+		sa.pair = M->pair;
+		sa.norm = o->norm;
+		sa.minLength = M->minLength;
+		sa.proxi = M->pair ? o->proxi : 0;
+		sa.etype = et;
+		sa.byteScale = bs;
+		int inc = 0;
+		if(!M->pair) {
+			inc = ccq_npos(M->incs, M->len);
+			fprintf(stderr, "# %d / %d bases included in distance matrix.\n", inc, M->len);
+		}
+		int rc = ccg_snp_ltd(ctx, &sa, D->mat, N ? N->mat : NULL, NULL);
+		if(rc) {
+			fprintf(stderr, "ccphylo_amd: distance computation failed: %s\n", ccg_strerror(rc));
+			return 1;
+		}
+		ccg_destroy(ctx);
+		D->n = n;
+		if(N) N->n = M->pair ? n : 0;
+	}
+	if(1 < D->n) {
+		ccq_print_phy(out, D, M->headers, NULL, NULL, o->flag, o->precision);
+		if(N && 1 < N->n) ccq_print_phy(out, N, M->headers, NULL, NULL, o->flag, o->precision);
+	}
+	if(out != stdout) fclose(out);
+	else fflush(stdout);
+	if(nout && nout != out && nout != stdout) fclose(nout);
+	ccq_ltd_free(D);
+	ccq_ltd_free(N);
+	ccq_msa_free(M);
+	return 0;
+}
+
+static int main_dist(int argc, char **argv) {
+	DistOpts o = {.outname = "-", .tmethod = "dnj", .method = "cos", .maxDist = 10.0, .minCov = 0.5, .minN = 1,
+	              .precision = 9, .transport = CCQ_TRANSPORT_RCCL, .flag = 1, .minLength = 1, .minDepth = 15,
+	              .threads = 1, .pr = {8, 1.0}};
+	const int rc = cli_parse(&dist_cmd, argc, argv, &o);
+	if(rc != CLI_GO) return rc;
+	if(o.minCov < 0 || 1 < o.minCov) die_opt("Invalid", "\"--min_cov\"");
+	if(o.pr.scale == 0) die_opt("Invalid", o.pr.mark == 2 ? "\"--short_precision\"" : "\"--byte_precision\"");
+	if(o.flag == (unsigned) -1) {
 		fprintf(stdout, "# Format flags output, add them to combine them.\n");
 		fprintf(stdout, "#\n");
 		fprintf(stdout, "#   1:\tRelaxed Phylip\n");
@@ -1192,7 +992,7 @@ static int main_dist(int argc, char **argv) {
 		fprintf(stdout, "#\n");
 		return 0;
 	}
-	if(!method) {
+	if(!o.method) {
 		fprintf(stdout, "# Distance calculation methods:\n");
 		fprintf(stdout, "#\n");
 		fprintf(stdout, "# cos:\tCalculate distance between positions as the angle between the count vectors.\n");
@@ -1212,133 +1012,57 @@ static int main_dist(int argc, char **argv) {
 	}
 	int metric;
 	unsigned lnorm = 0;
-	if(kma_metric_id(method, &metric, &lnorm)) die_opt("Invalid", "\"-d\"");
-	if(unsup) {
-		fprintf(stderr, "ccphylo_amd: dist option \"%s\" is not implemented by the GPU engine.\n", unsup);
+	if(kma_metric_id(o.method, &metric, &lnorm)) die_opt("Invalid", "\"-d\"");
+	if(o.unsup) {
+		fprintf(stderr, "ccphylo_amd: dist option \"%s\" is not implemented by the GPU engine.\n", o.unsup);
 		return 1;
 	}
-	if(methname && nfiles > 1 && !(tmpl && !(flag & 16) && first_byte(files[0]) != '>')) {
+	if(o.methname && o.files.n > 1 && !(o.tmpl && !(o.flag & 16) && first_byte(o.files.v[0]) != '>')) {
 		fprintf(stderr, "ccphylo_amd: -y with several FASTA files (-r) is not implemented by the GPU engine: use one MSA.\n");
 		return 1;
 	}
-	if(tmpl && nfiles > 1 && !(flag & 16) && first_byte(files[0]) != '>') {   /* dist.c:99-108: .mat input ignores -y */
-		return dist_kma(files, nfiles, tmpl, outname, noutname, metric, lnorm, norm, minDepth, minLength, minCov,
-		                flag, precision, et, bs, threads, device);
+	if(o.tmpl && o.files.n > 1 && !(o.flag & 16) && first_byte(o.files.v[0]) != '>') {   /* dist.c:99-108: .mat input ignores -y */
+		return dist_kma(&o, metric, lnorm);
 	}
-	if(tmpl && nfiles > 1) {
-		return dist_fsa_files(files, nfiles, tmpl, outname, noutname, flag, norm, minLength, minCov, proxi,
-		                      precision, et, bs, device);
-	}
-	if(nfiles > 1) {
+	if(o.tmpl && o.files.n > 1) return dist_fsa_files(&o);
+	if(o.files.n > 1) {
 		fprintf(stderr, "ccphylo_amd: multi-file dist input is not implemented by the GPU engine (use one MSA).\n");
 		return 1;
 	}
-	if(treename || dbname) {
-		return dist_tree(nfiles ? files[0] : "-", treename, tmethod, tflag, flag, norm, minLength, minCov, proxi,
-		                 precision, et, bs, threads, device, gpus, transport, fast, dbname, maxDist, minN, methname);
-	}
-	FILE *out = (outname[0] == '-' && outname[1] == 0) ? stdout : fopen(outname, "wb");
-	if(!out) {
-		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-		return 1;
-	}
-	FILE *nout = NULL;
-	if(noutname) {
-		/* dist.c:74-84 opens (truncates) it; cdist.c:367 then prints N to outfile */
-		if(!strcmp(noutname, outname)) nout = out;
-		else if(noutname[0] == '-' && noutname[1] == 0) nout = stdout;
-		else nout = fopen(noutname, "wb");
-	}
-	const char *in = nfiles ? files[0] : "-";
-	ccq_reader *r = ccq_open(in);
-	if(!r) {
-		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-		return 1;
-	}
-	if(!(flag & 16) && ccq_peek(r) != '>') {
-		fprintf(stderr, "ccphylo_amd: count-matrix (.mat) / union input is not implemented by the GPU engine.\n");
-		return 1;
-	}
-	/* the per-sequence work on host threads (fasta_par.c; the same result as
-	 * the serial ccq_load_msa) */
-	ccq_motif *mo = NULL;
-	const int nmo = methname ? load_motifs_or_die(methname, &mo) : 0;
-	ccq_msa *M = ccq_load_msa_par_meth(r, flag, minLength, minCov, proxi, threads > 16 ? (int) threads : 16, mo, nmo,
-	                                   stderr);
-	ccq_close(r);
-	if(apply_motifs(M, mo, nmo, device)) return 1;
-	free(mo);
-	int n = M->n;
-	if(n * (n - 1) / 2 < 1) {
-		fprintf(stderr, "Adjustning number of nodes to %d, to conform with the matrix size.\n", n * (n - 1) / 2);
-	}
-	ccq_ltd *D = ccq_ltd_new(n > 1 ? n : 2, et, bs), *N = NULL;
-	if(!n) {
-		fprintf(stderr, "All sequences were trimmed away.\n");
-		D->n = 0;
-	} else {
-		if(noutname) N = ccq_ltd_new(n > 1 ? n : 2, et, bs);
-		ccg_ctx *ctx = open_gpu(device);
-		ccg_snp_args sa;
-		memset(&sa, 0, sizeof(sa));
-		sa.n = n;
-		sa.len = M->len;
-		sa.stride = M->W;
-		sa.seqs = M->seqs;
-		sa.incs = M->incs;
-		sa.pair = M->pair;
-		sa.norm = norm;
-		sa.minLength = M->minLength;
-		sa.proxi = M->pair ? proxi : 0;
-		sa.etype = et;
-		sa.byteScale = bs;
-		int inc = 0;
-		if(!M->pair) {
-			inc = ccq_npos(M->incs, M->len);
-			fprintf(stderr, "# %d / %d bases included in distance matrix.\n", inc, M->len);
-		}
-		int rc = ccg_snp_ltd(ctx, &sa, D->mat, N ? N->mat : NULL, NULL);
-		if(rc) {
-			fprintf(stderr, "ccphylo_amd: distance computation failed: %s\n", ccg_strerror(rc));
-			return 1;
-		}
-		ccg_destroy(ctx);
-		D->n = n;
-		if(N) N->n = M->pair ? n : 0;
-	}
-	if(1 < D->n) {
-		ccq_print_phy(out, D, M->headers, NULL, NULL, flag, precision);
-		if(N && 1 < N->n) ccq_print_phy(out, N, M->headers, NULL, NULL, flag, precision);
-	}
-	if(out != stdout) fclose(out);
-	else fflush(stdout);
-	if(nout && nout != out && nout != stdout) fclose(nout);
-	ccq_ltd_free(D);
-	ccq_ltd_free(N);
-	ccq_msa_free(M);
-	return 0;
+	return (o.treename || o.dbname) ? dist_tree(&o) : dist_msa(&o);
 }
 
 /* ============================================================= tsv2phy */
-static int tsv2phy_help(FILE *out) {
-	fprintf(out, "#CCPhylo tsv2phy converts tsv files to phylip distance files.\n");
-	fprintf(out, "#   %-24s\t%-32s\t%s\n", "Options are:", "Desc:", "Default:");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'i', "input", "Input file", "stdin");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'o', "output", "Output file", "stdout");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'S', "separator", "Separator", "\\t");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'x', "print_precision", "Floating point print precision", "9");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'd', "distance", "Distance method", "cos");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'D', "distance_help", "Help on option \"-d\"", "");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'f', "flag", "Output flags", "1");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'F', "flag_help", "Help on option \"-f\"", "");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'p', "float_precision", "Float precision on distance matrix", "False / double");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 's', "short_precision", "Short precision on distance matrix", "False / double / 1e0");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'b', "byte_precision", "Byte precision on distance matrix", "False / double / 1e0");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'H', "mmap", "Allocate matrix on the disk", "False");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'T', "tmp", "Set directory for temporary files", "");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'h', "help", "Shows this helpmessage", "");
-	return out == stderr;
-}
+typedef struct {
+	const char *in, *outname, *method, *treename, *tmethod;
+	int flag, precision, vtype, device;
+	cli_prec scaled;   /* -s / -b were given; their value is not used */
+	char sep;
+} TsvOpts;
+
+#define F(f) offsetof(TsvOpts, f)
+static const cli_opt tsv2phy_opts[] = {
+	{'i', "input", CLI_STR, F(in), 0, "Input file", "stdin"},
+	{'o', "output", CLI_STR, F(outname), 0, "Output file", "stdout"},
+	{'S', "separator", CLI_CHAR, F(sep), 0, "Separator", "\\t"},
+	{'x', "print_precision", CLI_INT, F(precision), 0, "Floating point print precision", "9"},
+	{'d', "distance", CLI_STR, F(method), 0, "Distance method", "cos"},
+	{'D', "distance_help", CLI_UNSET, F(method), 0, "Help on option \"-d\"", ""},
+	{'f', "flag", CLI_INT, F(flag), 0, "Output flags", "1"},
+	{'F', "flag_help", CLI_FLAG, F(flag), -1, "Help on option \"-f\"", ""},
+	{'p', "float_precision", CLI_FLAG, F(vtype), 4, "Float precision on distance matrix", "False / double"},
+	{'s', "short_precision", CLI_PREC, F(scaled), 1, "Short precision on distance matrix", "False / double / 1e0"},
+	{'b', "byte_precision", CLI_PREC, F(scaled), 1, "Byte precision on distance matrix", "False / double / 1e0"},
+	{'H', "mmap", CLI_IGNORE, 0, 0, "Allocate matrix on the disk", "False"},   /* host memory knob: no effect on HBM */
+	{'T', "tmp", CLI_DROP, 0, 0, "Set directory for temporary files", ""},
+	{'h', "help", CLI_HELP, 0, 0, "Shows this helpmessage", ""},
+	{0, "tree", CLI_STR, F(treename)},
+	{0, "tree_method", CLI_STR, F(tmethod)},
+	{0, "device", CLI_INT, F(device)},
+	{0}};
+static const cli_cmd tsv2phy_cmd = {"#CCPhylo tsv2phy converts tsv files to phylip distance files.", tsv2phy_opts,
+                                    UNKNOWN_OWN, EXTRA_OWN, 1, 0, F(in)};
+#undef F
 
 /* -d of tsv2phy (tsv2phy.c:316-357) -> CCG_VEC_* and the exponent of l<n>;
  * exits like the reference's invaArg where it refuses too */
@@ -1373,85 +1097,17 @@ static int tsv_metric_id(const char *method, double *exponent) {
  * come from ccg_vec_ltd_dev and the LT stays in HBM: it is read back for the
  * Phylip text, and with --tree FILE handed to ccg_tree_dev in place */
 static int main_tsv2phy(int argc, char **argv) {
-	const char *in = "-", *outname = NULL, *method = "cos", *treename = NULL, *tmethod = "dnj";
-	int flag = 1, precision = 9, vtype = 8, device = 0, scaled = 0;
-	char sep = '\t';
-	Args A = {argc, 0, argv};
-	for(A.k = 1; A.k < argc; ++A.k) {
-		char *a = argv[A.k];
-		if(a[0] != '-' || a[1] == 0) {
-			in = a;
-			if(A.k + 1 < argc) {
-				fprintf(stderr, "Too many non-option arguments handed.\n");
-				return 1;
-			}
-			break;
-		}
-		if(a[1] == '-') {
-			char *name = a + 2, *eq = strchr(name, '=');
-			char *att = NULL;
-			if(eq) {
-				*eq = 0;
-				att = eq + 1;
-			}
-			if(*name == 0) { continue; }
-			else if(!strcmp(name, "input")) in = opt_value(&A, att, "input");
-			else if(!strcmp(name, "output")) outname = opt_value(&A, att, "output");
-			else if(!strcmp(name, "separator")) sep = opt_value(&A, att, "separator")[0];
-			else if(!strcmp(name, "print_precision")) precision = (int) opt_num(&A, att, "print_precision");
-			else if(!strcmp(name, "distance")) method = opt_value(&A, att, "distance");
-			else if(!strcmp(name, "distance_help")) method = NULL;
-			else if(!strcmp(name, "flag")) flag = (int) opt_num(&A, att, "flag");
-			else if(!strcmp(name, "flag_help")) flag = -1;
-			else if(!strcmp(name, "float_precision")) vtype = 4;
-			else if(!strcmp(name, "short_precision")) { scaled = 1; (void) opt_dvalue_def(&A, att, 1.0, "short_precision"); }
-			else if(!strcmp(name, "byte_precision")) { scaled = 1; (void) opt_dvalue_def(&A, att, 1.0, "byte_precision"); }
-			else if(!strcmp(name, "mmap")) { /* host memory knob: no effect on HBM */ }
-			else if(!strcmp(name, "tmp")) (void) opt_value(&A, att, "tmp");
-			else if(!strcmp(name, "tree")) treename = opt_value(&A, att, "tree");
-			else if(!strcmp(name, "tree_method")) tmethod = opt_value(&A, att, "tree_method");
-			else if(!strcmp(name, "device")) device = (int) opt_num(&A, att, "device");
-			else if(!strcmp(name, "help")) return tsv2phy_help(stdout);
-			else {
-				fprintf(stderr, "Unknown argument or option: \"%s\"\n", a);
-				return 1;
-			}
-			continue;
-		}
-		for(char *p = a + 1; *p; ++p) {
-			char o = *p, *att = p + 1;
-			int took = 1;
-			switch(o) {
-				case 'i': in = opt_value(&A, att, "i"); break;
-				case 'o': outname = opt_value(&A, att, "o"); break;
-				case 'S': sep = opt_value(&A, att, "S")[0]; break;
-				case 'x': precision = (int) opt_num(&A, att, "x"); break;
-				case 'd': method = opt_value(&A, att, "d"); break;
-				case 'f': flag = (int) opt_num(&A, att, "f"); break;
-				case 'T': (void) opt_value(&A, att, "T"); break;
-				case 's': scaled = 1; (void) opt_dvalue_def(&A, att, 1.0, "s"); break;
-				case 'b': scaled = 1; (void) opt_dvalue_def(&A, att, 1.0, "b"); break;
-				case 'D': method = NULL; took = 0; break;
-				case 'F': flag = -1; took = 0; break;
-				case 'p': vtype = 4; took = 0; break;
-				case 'H': took = 0; break;
-				case 'h': return tsv2phy_help(stdout);
-				default: {
-					fprintf(stderr, "Unknown argument or option: \"-%c\"\n", o);
-					return 1;
-				}
-			}
-			if(took) break;
-		}
-	}
-	if(flag == -1) {
+	TsvOpts o = {.in = "-", .method = "cos", .tmethod = "dnj", .flag = 1, .precision = 9, .vtype = 8, .sep = '\t'};
+	int rc = cli_parse(&tsv2phy_cmd, argc, argv, &o);
+	if(rc != CLI_GO) return rc;
+	if(o.flag == -1) {
 		fprintf(stdout, "Format flags output format, add them to combine them.\n");
 		fprintf(stdout, "#\n");
 		fprintf(stdout, "# 1:\tRelaxed Phylip\n");
 		fprintf(stdout, "#\n");
 		return 0;
 	}
-	if(!method) {
+	if(!o.method) {
 		fprintf(stdout, "# Distance calculation methods:\n");
 		fprintf(stdout, "#\n");
 		fprintf(stdout, "# cos:\tCalculate cosine distance between vectors.\n");
@@ -1464,8 +1120,8 @@ static int main_tsv2phy(int argc, char **argv) {
 		return 0;
 	}
 	double exponent;
-	const int metric = tsv_metric_id(method, &exponent);
-	if(scaled) {
+	const int metric = tsv_metric_id(o.method, &exponent);
+	if(o.scaled.mark) {
 		/* the reference's own short and byte rows are defective: tsv2phy.c:316-357
 		 * never sets distcmp_s, so -s computes cos whatever -d says; bc -b prints
 		 * all zeros and linf -b prints wrapped bytes (all three seen on a 7 x 5
@@ -1473,26 +1129,20 @@ static int main_tsv2phy(int argc, char **argv) {
 		fprintf(stderr, "ccphylo_amd: tsv2phy -s / -b is not supported: the reference's short and byte rows do not compute the chosen distance; use double or -p.\n");
 		return 1;
 	}
-	const int tm = treename ? fused_tree_method(tmethod) : 0;
+	const int tm = o.treename ? fused_tree_method(o.tmethod) : 0;
 	if(tm < 0) return 1;
-	ccq_reader *r = ccq_open(in);
-	if(!r) {
-		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-		return errno ? errno : 1;
-	}
+	ccq_reader *r = ccq_open(o.in);
+	if(!r) return errno_fail(1);
 	/* with --tree the Phylip text is written only where -o asks for it */
-	if(!outname && !treename) outname = "-";
+	if(!o.outname && !o.treename) o.outname = "-";
 	FILE *out = NULL, *tout = NULL;
-	if(outname) out = (outname[0] == '-' && outname[1] == 0) ? stdout : fopen(outname, "wb");
-	if(treename) tout = (treename[0] == '-' && treename[1] == 0) ? stdout : fopen(treename, "wb");
-	if((outname && !out) || (treename && !tout)) {
-		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-		return errno ? errno : 1;
-	}
+	if(o.outname) out = open_out(o.outname);
+	if(o.treename) tout = open_out(o.treename);
+	if((o.outname && !out) || (o.treename && !tout)) return errno_fail(1);
 	void *X = NULL;
 	int m = 0, n = 0;
 	char msg[256];
-	int rc = ccq_load_tsv(r, sep, vtype, &X, &m, &n, msg, sizeof(msg));
+	rc = ccq_load_tsv(r, o.sep, o.vtype, &X, &m, &n, msg, sizeof(msg));
 	ccq_close(r);
 	if(rc) {
 		fprintf(stderr, "%s\n", msg);
@@ -1502,25 +1152,25 @@ static int main_tsv2phy(int argc, char **argv) {
 		fprintf(stderr, "Input matrix contained zero rows.\n");
 		return 0;
 	}
-	if(treename && m < 3) {
+	if(o.treename && m < 3) {
 		fprintf(stderr, "ccphylo_amd: --tree needs at least 3 rows (%d).\n", m);
 		return 1;
 	}
 	const size_t cells = (size_t) m * (size_t) (m - 1) / 2;
 	double *D = out ? malloc((cells ? cells : 1) * sizeof(double)) : NULL;
-	ccg_join *joins = treename ? malloc((size_t) m * sizeof(ccg_join)) : NULL;
-	if((out && !D) || (treename && !joins)) {
+	ccg_join *joins = o.treename ? malloc((size_t) m * sizeof(ccg_join)) : NULL;
+	if((out && !D) || (o.treename && !joins)) {
 		fprintf(stderr, "Error: out of host memory\n");
 		return 12;
 	}
 	int nj = 0, fn = 0;
 	double fd = 0;
 	if(m > 1) {   /* a one-row table has no cell: nothing to launch */
-		ccg_ctx *ctx = open_gpu(device);
+		ccg_ctx *ctx = open_gpu(o.device);
 		void *dX = NULL, *dD = NULL;
 		char emsg[320] = "";
-		const size_t xb = (size_t) m * (size_t) n * (size_t) vtype;
-		ccg_vec_args va = {m, n, n, vtype, NULL, metric, exponent, 8};
+		const size_t xb = (size_t) m * (size_t) n * (size_t) o.vtype;
+		ccg_vec_args va = {m, n, n, o.vtype, NULL, metric, exponent, 8};
 		ccg_tree_args ta = {m, 8, 1.0, tm, 0, 1, 0, 0};
 		if((rc = ccg_malloc(ctx, &dX, xb)) || (rc = ccg_malloc(ctx, &dD, cells * sizeof(double))))
 			snprintf(emsg, sizeof(emsg), "device buffers: %s", ccg_strerror(rc));
@@ -1531,7 +1181,7 @@ static int main_tsv2phy(int argc, char **argv) {
 			else if(out && (rc = ccg_memcpy_d2h(ctx, D, dD, cells * sizeof(double))))
 				snprintf(emsg, sizeof(emsg), "read back: %s", ccg_strerror(rc));
 			/* the text first: the tree consumes the buffer */
-			else if(treename && (rc = ccg_tree_dev(ctx, &ta, dD, joins, &nj, &fn, &fd, NULL)))
+			else if(o.treename && (rc = ccg_tree_dev(ctx, &ta, dD, joins, &nj, &fn, &fd, NULL)))
 				snprintf(emsg, sizeof(emsg), "ccg_tree_dev: %s", ccg_strerror(rc));
 		}
 		if(dX) ccg_free(ctx, dX);
@@ -1544,11 +1194,11 @@ static int main_tsv2phy(int argc, char **argv) {
 	}
 	free(X);
 	if(out) {
-		ccq_print_tsvphy(out, D, 8, m, (unsigned) flag, precision);
+		ccq_print_tsvphy(out, D, 8, m, (unsigned) o.flag, o.precision);
 		if(out != stdout) fclose(out);
 		else fflush(stdout);
 	}
-	if(treename) {
+	if(o.treename) {
 		/* the names `tsv2phy | tree` would hold: the row indices as printed under -f */
 		char **names = malloc((size_t) m * sizeof(char *));
 		char *digits = malloc((size_t) m * 12);
@@ -1557,8 +1207,8 @@ static int main_tsv2phy(int argc, char **argv) {
 			snprintf(names[i], 12, "%d", i);
 		}
 		ccq_names *T = ccq_names_new(32, 4);   /* as tree.c:61-66 */
-		ccq_names_set(T, names, m, (unsigned) flag, '\t');
-		fused_write_newick(tout, T, m, joins, nj, fn, fd, 0, precision);
+		ccq_names_set(T, names, m, (unsigned) o.flag, '\t');
+		fused_write_newick(tout, T, m, &(Joins){joins, nj, fn, fd}, 0, o.precision);
 		fflush(stdout);
 		ccq_names_free(T);
 		free(names);
@@ -1570,86 +1220,38 @@ static int main_tsv2phy(int argc, char **argv) {
 }
 
 /* ============================================================ nwck2phy */
-static int nwck2phy_help(FILE *out) {
-	fprintf(out, "#CCPhylo nwck2phy converts newick files to phylip distance files.\n");
-	fprintf(out, "#   %-24s\t%-32s\t%s\n", "Options are:", "Desc:", "Default:");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'i', "input", "Input file", "stdin");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'o', "output", "Output file", "stdout");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'x', "print_precision", "Floating point print precision", "9");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'f', "flag", "Output flags", "1");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'F', "flag_help", "Help on option \"-f\"", "");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'p', "float_precision", "Float precision on distance matrix", "False / double");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 's', "short_precision", "Short precision on distance matrix", "False / double / 1e0");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'b', "byte_precision", "Byte precision on distance matrix", "False / double / 1e0");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'H', "mmap", "Allocate matrix on the disk", "False");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'T', "tmp", "Set directory for temporary files", "");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'h', "help", "Shows this helpmessage", "");
-	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "device", "GPU", "0");
-	return out == stderr;
-}
+typedef struct {
+	const char *in, *outname;
+	int flag, precision, device;
+	cli_prec pr;   /* etype; the scale is not used */
+} NwckOpts;
+
+#define F(f) offsetof(NwckOpts, f)
+static const cli_opt nwck2phy_opts[] = {
+	{'i', "input", CLI_STR, F(in), 0, "Input file", "stdin"},
+	{'o', "output", CLI_STR, F(outname), 0, "Output file", "stdout"},
+	{'x', "print_precision", CLI_INT, F(precision), 0, "Floating point print precision", "9"},
+	{'f', "flag", CLI_INT, F(flag), 0, "Output flags", "1"},
+	{'F', "flag_help", CLI_FLAG, F(flag), -1, "Help on option \"-f\"", ""},
+	{'p', "float_precision", CLI_FLAG, F(pr.mark), 4, "Float precision on distance matrix", "False / double"},
+	{'s', "short_precision", CLI_PREC, F(pr), 2, "Short precision on distance matrix", "False / double / 1e0"},
+	{'b', "byte_precision", CLI_PREC, F(pr), 1, "Byte precision on distance matrix", "False / double / 1e0"},
+	{'H', "mmap", CLI_IGNORE, 0, 0, "Allocate matrix on the disk", "False"},   /* host memory knob: no effect on HBM */
+	{'T', "tmp", CLI_DROP, 0, 0, "Set directory for temporary files", ""},
+	{'h', "help", CLI_HELP, 0, 0, "Shows this helpmessage", ""},
+	{0, "device", CLI_INT, F(device), 0, "GPU", "0"},
+	{0}};
+static const cli_cmd nwck2phy_cmd = {"#CCPhylo nwck2phy converts newick files to phylip distance files.", nwck2phy_opts,
+                                     UNKNOWN_CMDLINE, EXTRA_CMDLINE, 1, 0, F(in)};
+#undef F
 
 /* nwck2phy.c:33 newick2phy: every line's split list through ccg_nwck_ltd, printed by ccq_print_phy */
 static int main_nwck2phy(int argc, char **argv) {
-	const char *in = "-", *outname = "-";
-	int flag = 1, precision = 9, et = 8, device = 0;
-	Args A = {argc, 0, argv};
-	for(A.k = 1; A.k < argc; ++A.k) {
-		char *a = argv[A.k];
-		if(a[0] != '-' || a[1] == 0) {
-			in = a;
-			if(A.k + 1 < argc) {
-				fprintf(stderr, "Unexpected non-option argument(s).\n");
-				return 1;
-			}
-			break;
-		}
-		if(a[1] == '-') {
-			char *name = a + 2, *eq = strchr(name, '=');
-			char *att = NULL;
-			if(eq) {
-				*eq = 0;
-				att = eq + 1;
-			}
-			if(*name == 0) { continue; }
-			else if(!strcmp(name, "input")) in = opt_value(&A, att, "input");
-			else if(!strcmp(name, "output")) outname = opt_value(&A, att, "output");
-			else if(!strcmp(name, "print_precision")) precision = (int) opt_num(&A, att, "print_precision");
-			else if(!strcmp(name, "flag")) flag = (int) opt_num(&A, att, "flag");
-			else if(!strcmp(name, "flag_help")) flag = -1;
-			else if(!strcmp(name, "float_precision")) et = 4;
-			else if(!strcmp(name, "short_precision")) { et = 2; (void) opt_dvalue_def(&A, att, 1.0, "short_precision"); }
-			else if(!strcmp(name, "byte_precision")) { et = 1; (void) opt_dvalue_def(&A, att, 1.0, "byte_precision"); }
-			else if(!strcmp(name, "mmap")) { /* host memory knob: no effect on HBM */ }
-			else if(!strcmp(name, "tmp")) (void) opt_value(&A, att, "tmp");
-			else if(!strcmp(name, "device")) device = (int) opt_num(&A, att, "device");
-			else if(!strcmp(name, "help")) return nwck2phy_help(stdout);
-			else die_opt("Unknown", a);
-			continue;
-		}
-		for(char *p = a + 1; *p; ++p) {
-			char o = *p, *att = p + 1;
-			int took = 1;
-			switch(o) {
-				case 'i': in = opt_value(&A, att, "i"); break;
-				case 'o': outname = opt_value(&A, att, "o"); break;
-				case 'x': precision = (int) opt_num(&A, att, "x"); break;
-				case 'f': flag = (int) opt_num(&A, att, "f"); break;
-				case 'T': (void) opt_value(&A, att, "T"); break;
-				case 's': et = 2; (void) opt_dvalue_def(&A, att, 1.0, "s"); break;
-				case 'b': et = 1; (void) opt_dvalue_def(&A, att, 1.0, "b"); break;
-				case 'F': flag = -1; took = 0; break;
-				case 'p': et = 4; took = 0; break;
-				case 'H': took = 0; break;
-				case 'h': return nwck2phy_help(stdout);
-				default: {
-					char bad[3] = {'-', o, 0};
-					die_opt("Unknown", bad);
-				}
-			}
-			if(took) break;
-		}
-	}
-	if(flag == -1) {
+	NwckOpts o = {.in = "-", .outname = "-", .flag = 1, .precision = 9, .pr = {8, 1.0}};
+	const int prc = cli_parse(&nwck2phy_cmd, argc, argv, &o);
+	if(prc != CLI_GO) return prc;
+	const int et = o.pr.mark;
+	if(o.flag == -1) {
 		fprintf(stdout, "Format flags output format, add them to combine them.\n");
 		fprintf(stdout, "#\n");
 		fprintf(stdout, "# 1:\tRelaxed Phylip\n");
@@ -1661,16 +1263,10 @@ static int main_nwck2phy(int argc, char **argv) {
 		fprintf(stderr, "ccphylo_amd: nwck2phy with short / byte precision (-s / -b) is not implemented.\n");
 		return 1;
 	}
-	FILE *out = (outname[0] == '-' && outname[1] == 0) ? stdout : fopen(outname, "wb");
-	if(!out) {
-		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-		return errno ? errno : 1;
-	}
-	ccq_reader *r = ccq_open(in);
-	if(!r) {
-		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-		return errno ? errno : 1;
-	}
+	FILE *out = open_out(o.outname);
+	if(!out) return errno_fail(1);
+	ccq_reader *r = ccq_open(o.in);
+	if(!r) return errno_fail(1);
 	ccg_ctx *ctx = NULL;
 	ccq_ltd *D = ccq_ltd_new(128, et, 1.0);
 	ccq_str *header = ccq_new(64);
@@ -1692,14 +1288,14 @@ static int main_nwck2phy(int argc, char **argv) {
 		ccq_ltd_reserve(D, n);
 		D->n = n;
 		if(n > 1) {
-			if(!ctx) ctx = open_gpu(device);
+			if(!ctx) ctx = open_gpu(o.device);
 			const int grc = ccg_nwck_ltd(ctx, (const ccg_split *) splits, n - 1, et, D->mat);
 			if(grc) {
 				fprintf(stderr, "ccphylo_amd: nwck2phy failed: %s\n", ccg_strerror(grc));
 				return 1;
 			}
 		}
-		ccq_print_phy(out, D, names, NULL, (char *) header->seq, (unsigned) flag | CCQ_PHY_KEEP_DIRS, precision);
+		ccq_print_phy(out, D, names, NULL, (char *) header->seq, (unsigned) o.flag | CCQ_PHY_KEEP_DIRS, o.precision);
 		fflush(out);
 		ccq_newick_splits_free(names, splits, n);
 	}
@@ -1715,24 +1311,34 @@ static int main_nwck2phy(int argc, char **argv) {
 }
 
 /* ============================================================== phycmp */
-static int phycmp_help(FILE *out) {
-	fprintf(out, "# CCPhylo phycmp compares two distance matrices in phylip format.\n");
-	fprintf(out, "#   %-24s\t%-32s\t%s\n", "Options are:", "Desc:", "Default:");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'i', "input", "Input file(s)", "stdin");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'o', "output", "Output file", "stdout");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'S', "separator", "Separator", "\\t");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'f', "flag", "Output flags", "1");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'F', "flag_help", "Help on option \"-f\"", "");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'p', "float_precision", "Float precision on distance matrix", "False / double");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 's', "short_precision", "Short precision on distance matrix", "False / double / 1e0");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'b', "byte_precision", "Byte precision on distance matrix", "False / double / 1e0");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'H', "mmap", "Allocate matrix on the disk", "False");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'T', "tmp", "Set directory for temporary files", "");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'h', "help", "Shows this helpmessage", "");
-	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "by_name", "Match the second matrix's rows by name", "False");
-	fprintf(out, "#        --%-16s\t%-32s\t%s\n", "device", "GPU", "0");
-	return out == stderr;
-}
+typedef struct {
+	cli_list files;   /* none: stdin holds both matrices */
+	const char *outname;
+	int flag, device, by_name;
+	cli_prec pr;      /* etype; the scale is not used */
+	char sep;
+} PhycmpOpts;
+
+#define F(f) offsetof(PhycmpOpts, f)
+static const cli_opt phycmp_opts[] = {
+	{'i', "input", CLI_LIST, F(files), 0, "Input file(s)", "stdin", CLI_NEEDS_ONE},   /* cmdline.c:185, :216 */
+	{'o', "output", CLI_STR, F(outname), 0, "Output file", "stdout"},
+	{'S', "separator", CLI_CHAR, F(sep), 0, "Separator", "\\t"},
+	{'f', "flag", CLI_INT, F(flag), 0, "Output flags", "1"},
+	{'F', "flag_help", CLI_FLAG, F(flag), -1, "Help on option \"-f\"", ""},
+	{'p', "float_precision", CLI_FLAG, F(pr.mark), 4, "Float precision on distance matrix", "False / double"},
+	{'s', "short_precision", CLI_PREC, F(pr), 2, "Short precision on distance matrix", "False / double / 1e0"},
+	{'b', "byte_precision", CLI_PREC, F(pr), 1, "Byte precision on distance matrix", "False / double / 1e0"},
+	{'H', "mmap", CLI_IGNORE, 0, 0, "Allocate matrix on the disk", "False"},   /* host memory knob: no effect on HBM */
+	{'T', "tmp", CLI_DROP, 0, 0, "Set directory for temporary files", ""},
+	{'h', "help", CLI_HELP, 0, 0, "Shows this helpmessage", ""},
+	{0, "by_name", CLI_FLAG, F(by_name), 1, "Match the second matrix's rows by name", "False"},
+	{0, "device", CLI_INT, F(device), 0, "GPU", "0"},
+	{0}};
+/* non-options: the input files (phycmp.c:295) */
+static const cli_cmd phycmp_cmd = {"# CCPhylo phycmp compares two distance matrices in phylip format.", phycmp_opts,
+                                   UNKNOWN_CMDLINE, NULL, 1, 1, F(files)};
+#undef F
 
 typedef struct {
 	const char *name;
@@ -1781,81 +1387,11 @@ static int perm_by_name(char **names1, char **names2, int n, int32_t *perm, char
 
 /* phycmp.c:176 main_phycmp / :56 phyfilecmp: two matrices, one pass of ccg_ltd_cmp */
 static int main_phycmp(int argc, char **argv) {
-	const char *outname = "-", *files[2] = {"-", "-"};
-	int flag = 1, et = 8, device = 0, by_name = 0, nfiles = 0;
-	char sep = '\t';
-	Args A = {argc, 0, argv};
-	for(A.k = 1; A.k < argc; ++A.k) {
-		char *a = argv[A.k];
-		if(a[0] != '-' || a[1] == 0) {
-			/* non-options: the input files (phycmp.c:295) */
-			nfiles = 0;
-			for(; A.k < argc; ++A.k) {
-				if(nfiles < 2) files[nfiles] = argv[A.k];
-				++nfiles;
-			}
-			break;
-		}
-		char *att = NULL, o = 0;
-		int is_input = 0;
-		if(a[1] == '-') {
-			char *name = a + 2, *eq = strchr(name, '=');
-			if(eq) {
-				*eq = 0;
-				att = eq + 1;
-			}
-			if(*name == 0) { continue; }
-			else if(!strcmp(name, "input")) is_input = 1;
-			else if(!strcmp(name, "output")) outname = opt_value(&A, att, "output");
-			else if(!strcmp(name, "separator")) sep = opt_value(&A, att, "separator")[0];
-			else if(!strcmp(name, "flag")) flag = (int) opt_num(&A, att, "flag");
-			else if(!strcmp(name, "flag_help")) flag = -1;
-			else if(!strcmp(name, "float_precision")) et = 4;
-			else if(!strcmp(name, "short_precision")) { et = 2; (void) opt_dvalue_def(&A, att, 1.0, "short_precision"); }
-			else if(!strcmp(name, "byte_precision")) { et = 1; (void) opt_dvalue_def(&A, att, 1.0, "byte_precision"); }
-			else if(!strcmp(name, "mmap")) { /* host memory knob: no effect on HBM */ }
-			else if(!strcmp(name, "tmp")) (void) opt_value(&A, att, "tmp");
-			else if(!strcmp(name, "by_name")) by_name = 1;
-			else if(!strcmp(name, "device")) device = (int) opt_num(&A, att, "device");
-			else if(!strcmp(name, "help")) return phycmp_help(stdout);
-			else die_opt("Unknown", a);
-		} else {
-			for(char *p = a + 1; *p && !is_input; ++p) {
-				int took = 1;
-				o = *p;
-				att = p + 1;
-				switch(o) {
-					case 'i': is_input = 1; break;
-					case 'o': outname = opt_value(&A, att, "o"); break;
-					case 'S': sep = opt_value(&A, att, "S")[0]; break;
-					case 'f': flag = (int) opt_num(&A, att, "f"); break;
-					case 'T': (void) opt_value(&A, att, "T"); break;
-					case 's': et = 2; (void) opt_dvalue_def(&A, att, 1.0, "s"); break;
-					case 'b': et = 1; (void) opt_dvalue_def(&A, att, 1.0, "b"); break;
-					case 'F': flag = -1; took = 0; break;
-					case 'p': et = 4; took = 0; break;
-					case 'H': took = 0; break;
-					case 'h': return phycmp_help(stdout);
-					default: {
-						char bad[3] = {'-', o, 0};
-						die_opt("Unknown", bad);
-					}
-				}
-				if(took) break;
-			}
-		}
-		if(is_input) {
-			/* a list: the attached value or the next word, then every word that is no option (cmdline.c:185, :216) */
-			nfiles = 0;
-			files[nfiles++] = opt_value(&A, att, "input");
-			while(A.k + 1 < argc && (argv[A.k + 1][0] != '-' || argv[A.k + 1][1] == 0)) {
-				++A.k;
-				if(nfiles < 2) files[nfiles] = argv[A.k];
-				++nfiles;
-			}
-		}
-	}
-	if(flag == -1) {
+	PhycmpOpts o = {.outname = "-", .flag = 1, .pr = {8, 1.0}, .sep = '\t'};
+	const int prc = cli_parse(&phycmp_cmd, argc, argv, &o);
+	if(prc != CLI_GO) return prc;
+	const int et = o.pr.mark;
+	if(o.flag == -1) {
 		fprintf(stdout, "# Distance calculation methods:\n");
 		fprintf(stdout, "#\n");
 		fprintf(stdout, "# 1\tcos: Calculate cosine distance between vectors.\n");
@@ -1872,33 +1408,23 @@ static int main_phycmp(int argc, char **argv) {
 		fprintf(stderr, "ccphylo_amd: phycmp with short / byte precision (-s / -b) is not implemented.\n");
 		return 1;
 	}
-	if(nfiles > 2) {
+	if(o.files.n > 2) {
 		fprintf(stderr, "ccphylo_amd: phycmp takes two matrices: two files, or one file that holds both.\n");
 		return 1;
 	}
-	if(nfiles == 0) nfiles = 1;   /* stdin holds both */
-	FILE *out = (outname[0] == '-' && outname[1] == 0) ? stdout : fopen(outname, "wb");
-	if(!out) {
-		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-		return errno ? errno : 1;
-	}
-	ccq_reader *r = ccq_open(files[0]);
-	if(!r) {
-		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-		return errno ? errno : 1;
-	}
+	FILE *out = open_out(o.outname);
+	if(!out) return errno_fail(1);
+	ccq_reader *r = ccq_open(o.files.n ? o.files.v[0] : "-");
+	if(!r) return errno_fail(1);
 	ccq_ltd *D1 = ccq_ltd_new(32, et, 1.0), *D2 = ccq_ltd_new(32, et, 1.0);
 	ccq_names *T1 = ccq_names_new(32, 4), *T2 = ccq_names_new(32, 4);
 	int err = 0;
-	const int n1 = ccq_load_phy(r, D1, T1, sep, 0, &err);
-	if(nfiles != 1) {
+	const int n1 = ccq_load_phy(r, D1, T1, o.sep, 0, &err);
+	if(o.files.n == 2) {   /* else one file, or stdin, holds both */
 		ccq_close(r);
-		if(!(r = ccq_open(files[1]))) {
-			fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-			return errno ? errno : 1;
-		}
+		if(!(r = ccq_open(o.files.v[1]))) return errno_fail(1);
 	}
-	const int n2 = ccq_load_phy(r, D2, T2, sep, 0, &err);
+	const int n2 = ccq_load_phy(r, D2, T2, o.sep, 0, &err);
 	ccq_close(r);
 	/* phycmp.c:96-105 */
 	if(n1 <= 0 || n2 <= 0) {
@@ -1915,7 +1441,7 @@ static int main_phycmp(int argc, char **argv) {
 		nm2[i] = (char *) T2->names[i]->seq;
 	}
 	int32_t *perm = NULL;
-	if(by_name) {
+	if(o.by_name) {
 		char msg[512];
 		perm = malloc((size_t) n * sizeof(int32_t));
 		if(perm_by_name(nm1, nm2, n, perm, msg, sizeof(msg))) {
@@ -1935,14 +1461,14 @@ static int main_phycmp(int argc, char **argv) {
 		fprintf(stderr, "ccphylo_amd: phycmp: a matrix of one entry has no distance to compare.\n");
 		return 1;
 	}
-	ccg_ctx *ctx = open_gpu(device);
+	ccg_ctx *ctx = open_gpu(o.device);
 	ccg_cmp_sums sums;
 	const int rc = ccg_ltd_cmp(ctx, D1->mat, D2->mat, n, et, perm, &sums);
 	if(rc) {
 		fprintf(stderr, "ccphylo_amd: phycmp failed: %s\n", ccg_strerror(rc));
 		return 1;
 	}
-	ccq_print_phycmp(out, &sums, (int64_t) n * (n - 1) / 2, flag);
+	ccq_print_phycmp(out, &sums, (int64_t) n * (n - 1) / 2, o.flag);
 	if(out != stdout) fclose(out);
 	else fflush(stdout);
 	free(nm1);
@@ -1957,25 +1483,37 @@ static int main_phycmp(int argc, char **argv) {
 }
 
 /* =============================================================== merge */
-static int merge_help(FILE *out) {
-	fprintf(out, "#CCPhylo merges matrices from a multi Phylip file into one matrix\n");
-	fprintf(out, "#   %-24s\t%-32s\t%s\n", "Options are:", "Desc:", "Default:");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'i', "input", "Input multi phylip distance file", "stdin");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'o', "output", "Output file", "stdout");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'w', "nucleotides_weights", "Weigh distance with this Phylip file", "");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'n', "nucleotide_numbers", "Output number of nucleotides included", "False/None");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'S', "separator", "Separator", "\\t");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'x', "print_precision", "Floating point print precision", "9");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'f', "flag", "Output flags", "1");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'F', "flag_help", "Help on option \"-f\"", "");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'p', "float_precision", "Float precision on distance matrix", "double");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 's', "short_precision", "Short precision on distance matrix", "double / 1e0");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'b', "byte_precision", "Byte precision on distance matrix", "double / 1e0");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'H', "mmap", "Allocate matrix on the disk", "False");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'T', "tmp", "Set directory for temporary files", "");
-	fprintf(out, "#    -%c, --%-16s\t%-32s\t%s\n", 'h', "help", "Shows this helpmessage", "");
-	return out == stderr;
-}
+typedef struct {
+	const char *in, *outname, *wname, *nname, *treename, *tmethod;
+	int flag, precision, et, device;
+	cli_prec scaled;   /* -s / -b were given; their value is not used */
+	char sep;
+} MergeOpts;
+
+#define F(f) offsetof(MergeOpts, f)
+static const cli_opt merge_opts[] = {
+	{'i', "input", CLI_STR, F(in), 0, "Input multi phylip distance file", "stdin"},
+	{'o', "output", CLI_STR, F(outname), 0, "Output file", "stdout"},
+	{'w', "nucleotides_weights", CLI_STR, F(wname), 0, "Weigh distance with this Phylip file", ""},
+	{'n', "nucleotide_numbers", CLI_STR, F(nname), 0, "Output number of nucleotides included", "False/None"},
+	{'S', "separator", CLI_CHAR, F(sep), 0, "Separator", "\\t"},
+	{'x', "print_precision", CLI_INT, F(precision), 0, "Floating point print precision", "9"},
+	{'f', "flag", CLI_INT, F(flag), 0, "Output flags", "1"},
+	{'F', "flag_help", CLI_FLAG, F(flag), -1, "Help on option \"-f\"", ""},
+	{'p', "float_precision", CLI_FLAG, F(et), 4, "Float precision on distance matrix", "double"},
+	{'s', "short_precision", CLI_PREC, F(scaled), 1, "Short precision on distance matrix", "double / 1e0"},
+	{'b', "byte_precision", CLI_PREC, F(scaled), 1, "Byte precision on distance matrix", "double / 1e0"},
+	/* host memory knob: no effect on HBM.  -H ends its short-option word (-Hp does not reach p) */
+	{'H', "mmap", CLI_IGNORE, 0, 0, "Allocate matrix on the disk", "False", CLI_ENDS_WORD},
+	{'T', "tmp", CLI_DROP, 0, 0, "Set directory for temporary files", ""},
+	{'h', "help", CLI_HELP, 0, 0, "Shows this helpmessage", ""},
+	{0, "tree", CLI_STR, F(treename)},
+	{0, "tree_method", CLI_STR, F(tmethod)},
+	{0, "device", CLI_INT, F(device)},
+	{0}};
+static const cli_cmd merge_cmd = {"#CCPhylo merges matrices from a multi Phylip file into one matrix", merge_opts,
+                                  UNKNOWN_OWN, EXTRA_OWN, 1, 0, F(in)};
+#undef F
 
 /* The union's accumulators in HBM and the batch being staged (merge.c:122 /
  * :309 on the engine): every parsed matrix goes to the device at once and
@@ -2052,78 +1590,11 @@ static int merge_stage(MergeRun *R, const ccq_ltd *D, const ccq_ltd *W, int32_t 
 }
 
 static int main_merge(int argc, char **argv) {
-	const char *in = "-", *outname = NULL, *wname = NULL, *nname = NULL, *treename = NULL, *tmethod = "dnj";
-	int flag = 1, precision = 9, et = 8, device = 0, scaled = 0;
-	char sep = '\t';
-	Args A = {argc, 0, argv};
-	for(A.k = 1; A.k < argc; ++A.k) {
-		char *a = argv[A.k];
-		if(a[0] != '-' || a[1] == 0) {
-			in = a;
-			if(A.k + 1 < argc) {
-				fprintf(stderr, "Too many non-option arguments handed.\n");
-				return 1;
-			}
-			break;
-		}
-		if(a[1] == '-') {
-			char *name = a + 2, *eq = strchr(name, '=');
-			char *att = NULL;
-			if(eq) {
-				*eq = 0;
-				att = eq + 1;
-			}
-			if(*name == 0) { continue; }
-			else if(!strcmp(name, "input")) in = opt_value(&A, att, "input");
-			else if(!strcmp(name, "output")) outname = opt_value(&A, att, "output");
-			else if(!strcmp(name, "separator")) sep = opt_value(&A, att, "separator")[0];
-			else if(!strcmp(name, "print_precision")) precision = (int) opt_num(&A, att, "print_precision");
-			else if(!strcmp(name, "nucleotides_weights")) wname = opt_value(&A, att, "nucleotides_weights");
-			else if(!strcmp(name, "nucleotide_numbers")) nname = opt_value(&A, att, "nucleotide_numbers");
-			else if(!strcmp(name, "flag")) flag = (int) opt_num(&A, att, "flag");
-			else if(!strcmp(name, "flag_help")) flag = -1;
-			else if(!strcmp(name, "float_precision")) et = 4;
-			else if(!strcmp(name, "short_precision")) { scaled = 1; (void) opt_dvalue_def(&A, att, 1.0, "short_precision"); }
-			else if(!strcmp(name, "byte_precision")) { scaled = 1; (void) opt_dvalue_def(&A, att, 1.0, "byte_precision"); }
-			else if(!strcmp(name, "mmap")) { /* host memory knob: no effect on HBM */ }
-			else if(!strcmp(name, "tmp")) (void) opt_value(&A, att, "tmp");
-			else if(!strcmp(name, "tree")) treename = opt_value(&A, att, "tree");
-			else if(!strcmp(name, "tree_method")) tmethod = opt_value(&A, att, "tree_method");
-			else if(!strcmp(name, "device")) device = (int) opt_num(&A, att, "device");
-			else if(!strcmp(name, "help")) return merge_help(stdout);
-			else {
-				fprintf(stderr, "Unknown argument or option: \"%s\"\n", a);
-				return 1;
-			}
-			continue;
-		}
-		for(char *p = a + 1; *p; ++p) {
-			char o = *p, *att = p + 1;
-			int took = 1;
-			switch(o) {
-				case 'i': in = opt_value(&A, att, "i"); break;
-				case 'o': outname = opt_value(&A, att, "o"); break;
-				case 'S': sep = opt_value(&A, att, "S")[0]; break;
-				case 'x': precision = (int) opt_num(&A, att, "x"); break;
-				case 'w': wname = opt_value(&A, att, "w"); break;
-				case 'n': nname = opt_value(&A, att, "n"); break;
-				case 'f': flag = (int) opt_num(&A, att, "f"); break;
-				case 'T': (void) opt_value(&A, att, "T"); break;
-				case 's': scaled = 1; (void) opt_dvalue_def(&A, att, 1.0, "s"); break;
-				case 'b': scaled = 1; (void) opt_dvalue_def(&A, att, 1.0, "b"); break;
-				case 'F': flag = -1; took = 0; break;
-				case 'p': et = 4; took = 0; break;
-				case 'H': break;
-				case 'h': return merge_help(stdout);
-				default: {
-					fprintf(stderr, "Unknown argument or option: \"-%c\"\n", o);
-					return 1;
-				}
-			}
-			if(took) break;
-		}
-	}
-	if(flag == -1) {
+	MergeOpts o = {.in = "-", .tmethod = "dnj", .flag = 1, .precision = 9, .et = 8, .sep = '\t'};
+	const int prc = cli_parse(&merge_cmd, argc, argv, &o);
+	if(prc != CLI_GO) return prc;
+	const int et = o.et;
+	if(o.flag == -1) {
 		fprintf(stdout, "# Format flags output, add them to combine them.\n");
 		fprintf(stdout, "#\n");
 		fprintf(stdout, "#   1:\tRelaxed Phylip\n");
@@ -2135,33 +1606,30 @@ static int main_merge(int argc, char **argv) {
 		fprintf(stdout, "#\n");
 		return 0;
 	}
-	if(scaled) {
+	if(o.scaled.mark) {
 		/* merge.c:163-174 multiplies the scaled integers of d and w without unscaling them, and its
 		 * sums wrap: there is nothing to be compatible with */
 		fprintf(stderr, "ccphylo_amd: merge -s / -b is not supported: the reference multiplies the scaled integers of distance and weight without unscaling them; use double or -p.\n");
 		return 1;
 	}
-	const int tm = treename ? fused_tree_method(tmethod) : 0;
+	const int tm = o.treename ? fused_tree_method(o.tmethod) : 0;
 	if(tm < 0) return 1;
-	ccq_reader *r = ccq_open(in), *rw = wname ? ccq_open(wname) : NULL;
-	if(!r || (wname && !rw)) {
-		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-		return errno ? errno : 1;
-	}
+	ccq_reader *r = ccq_open(o.in), *rw = o.wname ? ccq_open(o.wname) : NULL;
+	if(!r || (o.wname && !rw)) return errno_fail(1);
 	MergeRun R;
 	memset(&R, 0, sizeof(R));
-	R.ctx = open_gpu(device);
+	R.ctx = open_gpu(o.device);
 	R.et = R.a.etype = et;
-	R.a.weighted = wname != NULL;
-	ccq_ltd *Dh = ccq_ltd_new(64, et, 1.0), *Wh = wname ? ccq_ltd_new(64, et, 1.0) : NULL;
+	R.a.weighted = o.wname != NULL;
+	ccq_ltd *Dh = ccq_ltd_new(64, et, 1.0), *Wh = o.wname ? ccq_ltd_new(64, et, 1.0) : NULL;
 	ccq_names *T = ccq_names_new(64, 32);
 	ccq_namemap *M = ccq_namemap_new();
 	int err = 0;
 	for(int mat = 0;; ++mat) {
-		const int m = ccq_load_phy(r, Dh, T, sep, 0, &err);
+		const int m = ccq_load_phy(r, Dh, T, o.sep, 0, &err);
 		if(mat && !m) break;   /* a size of 0 or the end of the file ends the input (merge.c:183) */
 		/* the weights' names overwrite the distances' (merge.c:144 / :184) */
-		if(Wh && ccq_load_phy(rw, Wh, T, sep, 0, &err) != m) {
+		if(Wh && ccq_load_phy(rw, Wh, T, o.sep, 0, &err) != m) {
 			fprintf(stderr, "Distance and included nucleotides does not concur!\n");
 			return 1;
 		}
@@ -2184,18 +1652,18 @@ static int main_merge(int argc, char **argv) {
 	ccq_close(r);
 	if(rw) ccq_close(rw);
 	const int n = ccq_namemap_n(M);
-	if(treename && n < 3) {
+	if(o.treename && n < 3) {
 		fprintf(stderr, "ccphylo_amd: --tree needs at least 3 entries (%d).\n", n);
 		return 1;
 	}
 	if(R.a.nsrc && merge_flush(&R, n)) return 1;
 	/* with --tree the Phylip texts are written only where -o / -n ask for them */
-	if(!outname && !treename) outname = "-";
-	if(wname && !nname && !treename) nname = "-";
-	if(!wname) nname = NULL;
+	if(!o.outname && !o.treename) o.outname = "-";
+	if(o.wname && !o.nname && !o.treename) o.nname = "-";
+	if(!o.wname) o.nname = NULL;
 	const size_t cells = (size_t) n * (size_t) (n ? n - 1 : 0) / 2;
-	ccq_ltd *Do = ccq_ltd_new(n > 1 ? n : 2, et, 1.0), *No = nname ? ccq_ltd_new(n > 1 ? n : 2, et, 1.0) : NULL;
-	ccg_join *joins = treename ? malloc((size_t) n * sizeof(ccg_join)) : NULL;
+	ccq_ltd *Do = ccq_ltd_new(n > 1 ? n : 2, et, 1.0), *No = o.nname ? ccq_ltd_new(n > 1 ? n : 2, et, 1.0) : NULL;
+	ccg_join *joins = o.treename ? malloc((size_t) n * sizeof(ccg_join)) : NULL;
 	int nj = 0, fn = 0, rc = 0;
 	double fd = 0;
 	Do->n = n;
@@ -2206,12 +1674,12 @@ static int main_merge(int argc, char **argv) {
 		if((rc = ccg_ltd_merge_close_dev(R.ctx, R.dD, R.dN, n, et))) return merge_fail("ccg_ltd_merge_close_dev", rc);
 		ccg_last_merge_ms(R.ctx, &ms);
 		R.dev_ms += ms;
-		if(outname && (rc = ccg_memcpy_d2h(R.ctx, Do->mat, R.dD, cells * (size_t) et))) return merge_fail("read back", rc);
+		if(o.outname && (rc = ccg_memcpy_d2h(R.ctx, Do->mat, R.dD, cells * (size_t) et))) return merge_fail("read back", rc);
 		if(No && (rc = ccg_memcpy_d2h(R.ctx, No->mat, R.dN, cells * (size_t) et))) return merge_fail("read back", rc);
 		/* the tree of `merge | tree`: cells as the Phylip text would round them, then the engine, which consumes D */
-		if(treename && (rc = ccg_round_decimal_dev(R.ctx, R.dD, (int64_t) cells, et, precision)))
+		if(o.treename && (rc = ccg_round_decimal_dev(R.ctx, R.dD, (int64_t) cells, et, o.precision)))
 			return merge_fail("ccg_round_decimal_dev", rc);
-		if(treename && (rc = ccg_tree_dev(R.ctx, &ta, R.dD, joins, &nj, &fn, &fd, NULL))) return merge_fail("ccg_tree_dev", rc);
+		if(o.treename && (rc = ccg_tree_dev(R.ctx, &ta, R.dD, joins, &nj, &fn, &fd, NULL))) return merge_fail("ccg_tree_dev", rc);
 	}
 	if(R.dD) ccg_free(R.ctx, R.dD);
 	if(R.dN) ccg_free(R.ctx, R.dN);
@@ -2220,23 +1688,20 @@ static int main_merge(int argc, char **argv) {
 	char **names = malloc(((size_t) n + 1) * sizeof(char *));
 	for(int i = 0; i < n; ++i) names[i] = strdup(ccq_namemap_name(M, i));
 	FILE *out = NULL, *nout = NULL, *tout = NULL;
-	if(outname) out = (outname[0] == '-' && outname[1] == 0) ? stdout : fopen(outname, "wb");
-	if(nname) nout = (nname[0] == '-' && nname[1] == 0) ? stdout : fopen(nname, "wb");
-	if(treename) tout = (treename[0] == '-' && treename[1] == 0) ? stdout : fopen(treename, "wb");
-	if((outname && !out) || (nname && !nout) || (treename && !tout)) {
-		fprintf(stderr, "Error: %d (%s)\n", errno, strerror(errno));
-		return errno ? errno : 1;
-	}
-	if(treename) {   /* the names `merge | tree` would hold, taken before the writer strips quotes */
+	if(o.outname) out = open_out(o.outname);
+	if(o.nname) nout = open_out(o.nname);
+	if(o.treename) tout = open_out(o.treename);
+	if((o.outname && !out) || (o.nname && !nout) || (o.treename && !tout)) return errno_fail(1);
+	if(o.treename) {   /* the names `merge | tree` would hold, taken before the writer strips quotes */
 		ccq_names *Tt = ccq_names_new(32, 4);   /* as tree.c:61-66 */
-		ccq_names_set(Tt, names, n, (unsigned) flag, '\t');
-		fused_write_newick(tout, Tt, n, joins, nj, fn, fd, 0, precision);
+		ccq_names_set(Tt, names, n, (unsigned) o.flag, '\t');
+		fused_write_newick(tout, Tt, n, &(Joins){joins, nj, fn, fd}, 0, o.precision);
 		fflush(stdout);
 		ccq_names_free(Tt);
 	}
-	if(out) ccq_print_phy(out, Do, names, NULL, "Merged", (unsigned) flag, precision);
+	if(out) ccq_print_phy(out, Do, names, NULL, "Merged", (unsigned) o.flag, o.precision);
 	if(nout) {
-		ccq_print_phy(nout, No, names, NULL, "Merged", (unsigned) flag, precision);
+		ccq_print_phy(nout, No, names, NULL, "Merged", (unsigned) o.flag, o.precision);
 		if(nout != stdout) fclose(nout);
 	}
 	if(out && out != stdout) fclose(out);
